@@ -7,8 +7,11 @@ exactly the work of one iteration of the reference's loop (trainer.py:42-56), on
 graph of the shape BASELINE.json names, inputs resident in HBM before the timed region.
 
     python bench.py [--gpus N --steps K --warmup W] [--workload yelp2018|amazon-book|synth-1M|synth-10M]
+                    [--full] [--dump-outputs DIR]
 
-Prints ONE JSON line (see DESIGN.md §Measurement for every field).
+Prints ONE JSON line (see DESIGN.md §Measurement for every field).  On one GPU a plain run sets up, warms up, times
+the K steps (and writes their outputs with --dump-outputs) and prints the line; --full adds every leg beside the
+headline (roofline, evaluation, epoch, CPU baseline, other configs, scale point, in-run traffic).
 """
 import argparse
 import json
@@ -30,6 +33,7 @@ INFINITY_CACHE_BYTES = 256 << 20
 # midpoints of the measured ranges): rows resident in the XCD's L2 16.8-18.8 TB/s; a 38 MB table out of the Infinity
 # Cache 8.6 TB/s; random whole rows of a buffer far beyond the Infinity Cache 5.5-5.8 TB/s.
 GATHER_L2_GBS, GATHER_MALL_GBS, GATHER_HBM_GBS = 17800.0, 8600.0, 5650.0
+DUMP_BYTES = 48 << 20  # --dump-outputs: the table is written whole up to this size, else a seeded sample of its rows
 
 
 def parse():
@@ -121,6 +125,15 @@ def parse():
     p.add_argument("--force-sharded", action="store_true",
                    help="run a multi-GPU path even at world size 1 (exercises the RCCL code path): the user-row-sharded one, "
                         "or the replicas with --parallel dp")
+    p.add_argument("--full", action="store_true",
+                   help="one-GPU line: after the timed region, also run every leg beside the headline (steady_state, roofline "
+                        "and its HBM / cache legs, evaluation, epoch, CPU baseline, the other configs, the scale point, the "
+                        "in-run traffic passes) as their own options select them.  Without it the run sets up, warms up, times "
+                        "--steps steps and prints the line: nothing else runs")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="one-GPU line: after the timed region, write what its last step computed as float32 .npy files under "
+                        "DIR: loss.npy (that step's loss terms) and params.npy (the [U+I, d] table after its Adam update), or, "
+                        "above %d MB, params_sample.npy (the rows of a fixed, seeded sample, ascending)" % (DUMP_BYTES >> 20))
     return p.parse_args()
 
 
@@ -575,6 +588,8 @@ def main():
     args = parse()
     if args.roofline_only:
         return roofline_only(args)
+    if args.dump_outputs and (args.gpus > 1 or args.force_sharded):
+        sys.exit("bench.py --dump-outputs: the one-GPU line only (a multi-GPU run's tables are spread over its ranks)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         self_launch(args)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not args.worker and os.environ.get("IDG_BENCH_SUPERVISE", "1") != "0":
@@ -674,6 +689,8 @@ def main():
     default_headline = args.workload == "yelp2018" and args.dim == 64 and args.model == "LightGCN" and args.layers == 3
     if args.steady_steps < 0:
         args.steady_steps = 500 if default_headline else 0
+    # (the steady-state steps run with --full only, but their batches are drawn either way: a run's inputs, and so what
+    #  --dump-outputs writes, do not depend on --full)
     wl = build_workload(args, rank, world)
     U, I, d, K, B = wl["U"], wl["I"], args.dim, args.layers, args.batch
     n, nnz = U + I, len(wl["indices"])
@@ -718,7 +735,7 @@ def main():
     # (the ramp's panel has a different width than the bench's, so its launches are another instantiation of the kernel
     #  and stay out of the measured kernel's row in a per-kernel trace of this command)
     S.ramp_clocks(graph=graph if graph is not None and nnz * d <= 4e9 and args.ramp == "graph" else None, d=32 if d != 32 else 64)
-    if graph is not None and args.model == "LightGCN":
+    if args.full and graph is not None and args.model == "LightGCN":
         for k in range(1, K):
             eng.forward_layer(k)  # allocates the two layer buffers of the launch-timing leg BEFORE the timed region (at
             #                       config-5 size: 2 x 15 GB of hipMalloc, ~1 s)
@@ -735,9 +752,11 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     plan1 = eng._plan.stats() if getattr(eng, "_plan", None) is not None else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng.params, losses[args.warmup + args.steps - 1])
 
     steady = None
-    if args.steady_steps >= 100:
+    if args.full and args.steady_steps >= 100:
         # the driver times 20 steps (5 ms): a 2 % round-to-round delta cannot be told from box noise there.  500 further
         # steps of the same loop, in 50-step windows between HIP events on the step's stream (no host synchronisation in
         # between: the pipeline stays full), give the spread
@@ -791,16 +810,19 @@ def main():
         out["steady_state"] = steady
     if graph is not None and args.model == "LightGCN" and K >= 2:
         out["step_bytes"] = step_bytes(wl, n, nnz, d, K, B, ms_per_step)
+    out["sampler"] = {"value": wl["sampler_rate"], "unit": "triples/s", "what": "native MT19937 sampler + shuffle permutation, "
+                      "bit-identical to the reference's NumPy stream, one host core"}
+    if not args.full:
+        args.emit(out)
+        return
     hbm_leg = False
     if graph is not None:
         out["roofline"] = roofline(args, eng, graph, n, nnz, d, K, args.workload, in_step_form=(args.model == "LightGCN"),
                                    bitmap=eng.touched)
         hbm_leg = args.hbm_leg == "on" or (args.hbm_leg == "auto" and args.workload == "yelp2018" and d == 64
                                            and args.model == "LightGCN")
-    # beside the headline: the host sampler's own rate, and full-rank evaluation (propagate + fused
-    # score/mask/top-20 of every user against the train CSR) on the same tables — both outside the timed region
-    out["sampler"] = {"value": wl["sampler_rate"], "unit": "triples/s", "what": "native MT19937 sampler + shuffle permutation, "
-                      "bit-identical to the reference's NumPy stream, one host core"}
+    # beside the headline: full-rank evaluation (propagate + fused score/mask/top-20 of every user against
+    # the train CSR) on the same tables, outside the timed region
     if U * I <= 4e10:
         with torch.no_grad():
             fin = eng.propagate(force=True)
@@ -869,6 +891,23 @@ def main():
             out["roofline"]["traffic_in_run_error"] = "%s: %s" % (type(exc).__name__, str(exc)[:300])
     flatten_north_star(out)
     args.emit(out)
+
+
+def dump_outputs(path, params, loss):
+    """--dump-outputs: what the timed region's last step handed back, as float32 .npy files under `path`: loss.npy = that
+    step's loss terms (BPR, L2[, InfoNCE]); params.npy = the [U+I, d] table after its Adam update, or, when that is larger
+    than DUMP_BYTES, params_sample.npy = the rows of a fixed sample (numpy seed 0, row ids ascending).  A run's inputs
+    follow from its arguments alone, so the files of two builds can be compared one for one."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy())
+    n, d = params.shape
+    if n * d * 4 <= DUMP_BYTES:
+        np.save(os.path.join(path, "params.npy"), params.detach().float().cpu().numpy())
+    else:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=DUMP_BYTES // (4 * d), replace=False))
+        sample = params.detach()[torch.from_numpy(rows).to(params.device)]
+        np.save(os.path.join(path, "params_sample.npy"), sample.float().cpu().numpy())
 
 
 def flatten_north_star(out):
@@ -998,7 +1037,7 @@ def _pmc_dir(args, create=False):
 def _pmc_wanted(args):
     import shutil
 
-    if args.pmc == "off" or getattr(args, "roofline_only", None):
+    if args.pmc == "off" or getattr(args, "roofline_only", None) or not getattr(args, "full", False):
         return False
     default_headline = args.workload == "yelp2018" and args.dim == 64 and args.model == "LightGCN" and args.layers == 3
     return (args.pmc == "on" or default_headline) and shutil.which("rocprofv3") is not None

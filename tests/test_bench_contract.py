@@ -27,8 +27,8 @@ def _env():
 
 @pytest.mark.gpu
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "medium", "--steps", "6", "--warmup", "2", "--cpu-seconds", "1",
-                        "--hbm-leg", "off", "--epoch-leg", "off"], cwd=ROOT, env=_env(), capture_output=True, text=True,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--workload", "medium", "--steps", "6", "--warmup", "2", "--cpu-seconds",
+                        "1", "--hbm-leg", "off", "--epoch-leg", "off"], cwd=ROOT, env=_env(), capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _one_line(r.stdout)
@@ -48,14 +48,41 @@ def test_single_gpu_line():
 
 
 @pytest.mark.gpu
+def test_plain_line_times_the_steps_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the one-GPU line holds the headline alone (no leg beside it runs), and --dump-outputs writes the last
+    timed step's loss terms and table: the same files, bit for bit, from two runs with the same arguments."""
+    import numpy as np
+
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--workload", "medium", "--steps", "5", "--warmup", "2", "--dump-outputs",
+                            str(tmp_path / run)], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(_one_line(r.stdout))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - d["config"]["batch"] * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    for k in ("roofline", "cpu_baseline", "eval", "epoch", "configs", "scale_point", "steady_state"):
+        assert k not in d, k
+    assert lines[1]["loss_first_last"] == d["loss_first_last"]
+    loss, params = (np.load(tmp_path / "a" / f) for f in ("loss.npy", "params.npy"))
+    assert loss.dtype == np.float32 and loss.shape == (2,) and params.dtype == np.float32 and params.shape[1] == 64
+    assert np.isfinite(params).all() and abs(float(loss.sum()) - d["loss_first_last"][1]) <= 1e-6 * abs(d["loss_first_last"][1])
+    for f in ("loss.npy", "params.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+
+
+@pytest.mark.gpu
 def test_headline_carries_the_other_configs_steady_state_and_in_run_traffic():
-    """The default headline's extra fields on a cut-down run (no synth-10M legs): `configs` = one measured leg for each of
+    """The default headline's extra fields (--full) on a cut-down run (no synth-10M legs): `configs` = one measured leg for each of
     BASELINE configs[0], [2], [3] with its own roofline object and CPU leg; `steady_state` (50-step windows); the step as
     ONE library call with the host's busy time; and `roofline.traffic` MEASURED IN THIS RUN by rocprofv3 children (when the
     profiler is on PATH), the file-based figure kept beside it."""
     import shutil
 
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1", "--hbm-leg", "off",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1", "--hbm-leg", "off",
                         "--scale-point", "off", "--epoch-leg", "off", "--configs-leg", "on", "--pmc", "on", "--steady-steps", "200"],
                        cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
