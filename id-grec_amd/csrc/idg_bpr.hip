@@ -814,6 +814,13 @@ int idg::bpr_plan_rows(const int64_t* users, const int64_t* pos, const int64_t* 
                        one_launch_sort);
 }
 
+void idg::bpr_plan_lists(const void* ws, int64_t B, const int32_t** skeys, const int32_t** sslots) {
+  const BprWs w = bpr_layout(B, sort_temp_bytes(3 * B));
+  const char* base = reinterpret_cast<const char*>(ws);
+  *skeys = reinterpret_cast<const int32_t*>(base + w.skeys);
+  *sslots = reinterpret_cast<const int32_t*>(base + w.sslots);
+}
+
 extern "C" {
 
 size_t idg_bpr_workspace_bytes(int64_t B, int64_t d) {

@@ -35,6 +35,9 @@ void rows_changed(const void* bitmap, size_t bytes = 0);
 // has slack); idg_graph_live_units without its own clearing of that header.
 int bpr_plan_rows(const int64_t* users, const int64_t* pos, const int64_t* neg, int64_t B, int64_t num_users, int64_t n, void* ws,
                   uint32_t* bitmap, uint32_t* zero2, bool one_launch_sort, void* stream);
+// The sorted (row, slot) lists of a plan idg_bpr_plan_f32 left in a BPR workspace of batch size B (idg_au.hip scatters
+// through the plan of (users, pos, pos)).
+void bpr_plan_lists(const void* ws, int64_t B, const int32_t** skeys, const int32_t** sslots);
 int live_units_prezeroed(const idg_graph* g, const uint32_t* bitmap, void* units_ws, int64_t max_rows, void* stream);
 
 }  // namespace idg

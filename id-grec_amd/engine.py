@@ -146,6 +146,8 @@ class PropagationEngine:
         self.ssl = None        # (eps, temperature, ssl_lambda): SimGCL's perturbed views + InfoNCE inside the fused step
         self.xssl = None       # the same triple for XSimGCL (one perturbed pass, cl_layer = 1)
         self.sgl = None        # (temperature, ssl_lambda, sub_graph_1, sub_graph_2): SGL's two edge-dropped views
+        self.au = None         # (gamma,): DirectAU — alignment + uniformity over (user, positive) rows replaces BPR; the
+        #                        batch's rows are users and positives (negatives ignored: the slots are prepared with neg := pos)
         self._views = self._ssl_loss = None
         # one library call per step (StepPlan / idg_step_run_f32) for the plain LightGCN / MFBPR step; IDG_STEP_PLAN=0: the
         # call-by-call chain below (same kernels, same bits)
@@ -203,6 +205,8 @@ class PropagationEngine:
             self.stamp = 0    # order of last hand-out (the ring recycles the oldest)
 
     def _prepare(self, slot, users, pos, neg):
+        if self.au is not None:
+            neg = pos  # bitmap and scatter plan of users and positives only (idg_align_uniform_f32's plan form)
         main = torch.cuda.current_stream()
         B = users.shape[0]
         slot.ssl_key = None  # a plan is honoured for the batch it was built for only: set again below
@@ -291,7 +295,7 @@ class PropagationEngine:
         """The one-call step covers the plain form: deterministic scatter, Adam in the epilogue, no SSL views, no gradient
         exchange, no receptive-field restriction (graphs >= 4 M rows), a tiled width."""
         if not (self._plan_on and self.deterministic and self.fuse_adam and self.ssl is None and self.xssl is None
-                and self.sgl is None and self.exchange is None and not self._compact):
+                and self.sgl is None and self.au is None and self.exchange is None and not self._compact):
             return False
         if self.graph is None:
             return self.d % 4 == 0 and self.d <= 1024  # idg_step_create / idg_adam_rows_f32's limits (ADVICE r05)
@@ -351,11 +355,17 @@ class PropagationEngine:
         With self.ssl set (SimGCL): two noise-perturbed encoder passes next to the clean one, InfoNCE between
         them over the batch's unique users / positive items, its gradients added (times ssl_lambda) to the BPR
         gradient before the ONE backward propagation all three passes share; loss gets a third entry."""
-        three = self.ssl is not None or self.xssl is not None or self.sgl is not None
+        three = self.ssl is not None or self.xssl is not None or self.sgl is not None or self.au is not None
         loss = (self._loss3 if three else self.loss) if loss_out is None else loss_out
         main = torch.cuda.current_stream()
+        if self.au is not None:
+            neg = pos  # (the slot key and plan of a DirectAU batch: see _prepare)
         if self.graph is None:
             self.grad.zero_()
+            if self.au is not None and not self.deterministic:
+                ops.align_uniform_raw(self.params, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.grad,
+                                      self.grad, loss=loss)
+                return loss
             if not self.deterministic:
                 ops.bpr_fused_raw(self.params, self.params, users, pos, neg, self.U, self.reg_lambda, self.grad,
                                   self.grad, loss=loss, deterministic=0)
@@ -369,8 +379,12 @@ class PropagationEngine:
                 self._prepare(slot, users, pos, neg)
             slot.key = None
             slot.plan_done.wait(main.cuda_stream)
-            ops.bpr_fused_raw(self.params, self.params, users, pos, neg, self.U, self.reg_lambda, self.grad,
-                              self.grad, loss=loss, deterministic=2, ws=slot.ws)
+            if self.au is not None:
+                ops.align_uniform_raw(self.params, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.grad,
+                                      self.grad, loss=loss, plan_ws=slot.ws)
+            else:
+                ops.bpr_fused_raw(self.params, self.params, users, pos, neg, self.U, self.reg_lambda, self.grad,
+                                  self.grad, loss=loss, deterministic=2, ws=slot.ws)
             slot.free = slot.free_ev
             slot.free.record(main.cuda_stream)
             self._final_version = -1
@@ -379,8 +393,12 @@ class PropagationEngine:
             self.grad.zero_()
             self.g_final.zero_()
             self.graph.propagate_mean_raw(self.params, self.K, self.inc, out=self.final)
-            ops.bpr_fused_raw(self.final, self.params, users, pos, neg, self.U, self.reg_lambda, self.g_final,
-                              self.grad, loss=loss, deterministic=0)
+            if self.au is not None:
+                ops.align_uniform_raw(self.final, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.g_final,
+                                      self.grad, loss=loss)
+            else:
+                ops.bpr_fused_raw(self.final, self.params, users, pos, neg, self.U, self.reg_lambda, self.g_final,
+                                  self.grad, loss=loss, deterministic=0)
             self.graph.propagate_mean_bwd_raw(self.g_final, self.K, self.inc, out=self.grad, accumulate=True)
             self._final_version = -1
             return loss
@@ -450,13 +468,19 @@ class PropagationEngine:
         assert self.exchange is None or not three, "gradient-row exchange: LightGCN-family steps only"
         if not ahead:
             slot.plan_done.wait(main.cuda_stream)
+        if self.au is not None:
+            # DirectAU: the alignment / uniformity call in place of the BPR scatter; its rows of g_final and self.grad are
+            # stored (accumulate=False) — exactly the bitmap's rows, the contract the backward propagation below reads
+            ops.align_uniform_raw(self.final, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.g_final,
+                                  self.grad, loss=loss[:3], accumulate=False, plan_ws=slot.ws)
         # reached rows of g_final and of the regulariser gradient (self.grad) are STORED and the backward
         # propagation reads flagged rows only: neither panel is ever zero-filled
         # (the bitmap already holds the batch's rows: with TOUCHED_PRESET the scatter stores its rows without writing it, so
         #  the lists registered for it — the compacted inputs of the first backward product — stay valid)
-        ops.bpr_fused_raw(self.final, self.params, users, pos, neg, self.U, self.reg_lambda, self.g_final,
-                          self.grad, loss=loss[:2], deterministic=2 | native.IDG_BPR_TOUCHED_PRESET, touched=slot.bitmap,
-                          ws=slot.ws)
+        else:
+            ops.bpr_fused_raw(self.final, self.params, users, pos, neg, self.U, self.reg_lambda, self.g_final,
+                              self.grad, loss=loss[:2], deterministic=2 | native.IDG_BPR_TOUCHED_PRESET, touched=slot.bitmap,
+                              ws=slot.ws)
         if self.ssl is not None:
             # d(ssl_lambda * InfoNCE)/d view_1 + d(...)/d view_2 join the BPR gradient in g_final's (stored) rows
             ops.infonce_pair_raw(self._views[0], self._views[1], users, pos, self.U, temperature, g1=self.g_final,

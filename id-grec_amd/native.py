@@ -106,6 +106,9 @@ PROTOTYPES = {
                                     c_vp, c_vp, c_vp]),
     "idg_ngcf_tail_bwd_f32": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_uint64, C.c_uint64,
                                         c_vp, c_vp]),
+    "idg_align_uniform_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "idg_align_uniform_f32": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float,
+                                        C.c_float, c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp]),
     "idg_infonce_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "idg_infonce_cross_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float, c_vp, c_vp,
                                         C.c_float, c_vp, c_vp]),
@@ -243,7 +246,7 @@ except ImportError:  # host-only use (sampler / parser / adjacency) works withou
     _torch = None
 
 ACT_TANH, ACT_TANH_BWD = 1, 2  # idg_epilogue.act
-ABI_VERSION = 140  # include/idgrec.h IDG_VERSION the prototype table above was written against
+ABI_VERSION = 141  # include/idgrec.h IDG_VERSION the prototype table above was written against
 
 lib = C.CDLL(LIB_PATH)
 lib.idg_version.restype = C.c_int

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define IDG_VERSION 140 /* 0.5.1: idg_pack24_f32 / idg_unpack24_f32 / idg_reduce24_f32 / idg_alltoall_f32 (24-bit panel exchange, rank-ordered sum), idg_score_topk_candidate_counts, idg_score_topk_option (the top-K knobs: environment read once), idg_score_topk_info fills info[8], form 3's whole-call fall-back; idg_step_run_f32 takes next_ids_token; idg_step_synchronize also drains the side stream's preparations; 0.5.0: idg_step_* (one library call per training step), idg_adam_rows_f32; 0.4.4: IDG_ADAM_DISCARD_GRAD; 0.4.3: idg_event_synchronize; 0.4.2: idg_infonce_plan / IDG_SSL_PLANNED / idg_infonce_cross_ex_f32 (InfoNCE id lists a batch ahead); 0.4.1: idg_ngcf_layer_fwd_f32 / idg_ngcf_layer_bwd_f32 (one kernel per NGCF layer and direction); 0.4.0: idg_rows_layer_mean_n_f32 (any number of layers), idg_flags_compact_f32 (the touched-item
+#define IDG_VERSION 141 /* 0.5.2: idg_align_uniform_f32 / idg_align_uniform_workspace_bytes (DirectAU's alignment + uniformity loss); 0.5.1: idg_pack24_f32 / idg_unpack24_f32 / idg_reduce24_f32 / idg_alltoall_f32 (24-bit panel exchange, rank-ordered sum), idg_score_topk_candidate_counts, idg_score_topk_option (the top-K knobs: environment read once), idg_score_topk_info fills info[8], form 3's whole-call fall-back; idg_step_run_f32 takes next_ids_token; idg_step_synchronize also drains the side stream's preparations; 0.5.0: idg_step_* (one library call per training step), idg_adam_rows_f32; 0.4.4: IDG_ADAM_DISCARD_GRAD; 0.4.3: idg_event_synchronize; 0.4.2: idg_infonce_plan / IDG_SSL_PLANNED / idg_infonce_cross_ex_f32 (InfoNCE id lists a batch ahead); 0.4.1: idg_ngcf_layer_fwd_f32 / idg_ngcf_layer_bwd_f32 (one kernel per NGCF layer and direction); 0.4.0: idg_rows_layer_mean_n_f32 (any number of layers), idg_flags_compact_f32 (the touched-item
                            agreement without a host read-back), idg_shard_prepare validates its geometry.
                            133 / 0.3.0: process-wide live-unit registry + idg_graph_live_units_check; idg_spmm_epi_f32 (every
                            epilogue option; out_rows and x_rows combined); round-3 sharded step: idg_rows_gather2 / _scatter /
@@ -617,6 +617,28 @@ int idg_infonce_plan(const int64_t* users, const int64_t* items, int64_t B, int6
 int idg_infonce_cross_ex_f32(const float* view, int64_t n, int64_t d, const int64_t* users, const int64_t* items,
                              int64_t B, int64_t num_users, float temperature, float* loss, float* g, float grad_scale,
                              int planned, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * DEVICE: alignment + uniformity loss (DirectAU, Wang et al. KDD'22; models/DirectAU.py:59-79 of the reference) and
+ * its gradients in one call.  a_i = normalize(final[users[i]]), b_i = normalize(final[num_users + pos[i]]) with
+ * normalize(x) = x / max(||x||, 1e-12):
+ *   loss[0] = mean_i ||a_i - b_i||^2
+ *   loss[1] = gamma (unif(a) + unif(b)) / 2,  unif(x) = log(sum_{i<j} exp(-2 ||x_i - x_j||^2) / (B (B - 1) / 2))
+ *             (NaN for B = 1, as torch.pdist's empty mean; the term then contributes no gradient)
+ *   loss[2] = reg_lambda (||ego[users]||^2 / 2B + ||ego[num_users + pos]||^2 / 2B)
+ * g_final (nullable): d (up[0] loss[0] + up[1] loss[1]) / d final; g_ego (nullable): d (up[2] loss[2]) / d ego, where
+ * upstream is a DEVICE pointer to the three incoming gradient scalars up[0..2] or NULL for ones; both the same buffer when
+ * final == ego (the MF encoder).  Occurrences of one row are added in batch order (run-to-run reproducible).  Rows the
+ * batch touches are ADDED into (accumulate != 0) or STORED (accumulate = 0: the rows of idg_bpr_touch_rows(users, pos,
+ * pos), nothing else written).  The B x B pair matrix is never stored: ws is O(B d)
+ * (idg_align_uniform_workspace_bytes).  plan_ws: NULL, or a BPR workspace (idg_bpr_workspace_bytes(B, d)) holding
+ * idg_bpr_plan_f32(users, pos, pos, ...) of THIS batch — the index-only stage done ahead on another stream.
+ * ---------------------------------------------------------------------------------- */
+size_t idg_align_uniform_workspace_bytes(int64_t B, int64_t d);
+int idg_align_uniform_f32(const float* final_panel, const float* ego_panel, int64_t n, int64_t d,
+                          const int64_t* users, const int64_t* pos, int64_t B, int64_t num_users,
+                          float gamma, float reg_lambda, float* loss, const float* upstream, float* g_final, float* g_ego,
+                          int accumulate, const void* plan_ws, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * DEVICE: dense Adam step  (torch.optim.Adam defaults, utility/utility_train/trainer.py:11,56:

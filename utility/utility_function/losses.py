@@ -4,7 +4,8 @@
 reference and are plain torch expressions (they serve models that gather on their own, e.g.
 NGCF-style encoders).  The LightGCN / MFBPR / SimGCL models do not come through here for
 their main loss: they call `idgrec_amd.ops.bpr_loss`, which fuses gather + both losses +
-gradients in one HIP kernel chain.
+gradients in one HIP kernel chain; DirectAU likewise calls `idgrec_amd.ops.align_uniform_loss`
+for its `get_align_loss` / `get_uniform_loss` terms.
 """
 import torch
 
@@ -39,3 +40,18 @@ def get_InfoNCE_loss_all(embedding_1, embedding_2, embedding_2_all, temperature)
     every = torch.nn.functional.normalize(embedding_2_all)
     ttl = torch.exp(torch.matmul(a, every.transpose(0, 1)) / temperature).sum(dim=1)
     return torch.mean(-torch.log(pos / ttl + 10e-8))
+
+
+def get_align_loss(embedding_1, embedding_2):
+    """DirectAU's alignment: mean squared distance between the L2-normalised rows of the two blocks."""
+    a = torch.nn.functional.normalize(embedding_1, dim=-1)
+    b = torch.nn.functional.normalize(embedding_2, dim=-1)
+    return (a - b).square().sum(dim=1).mean()
+
+
+def get_uniform_loss(embedding):
+    """DirectAU's uniformity: log of the mean Gaussian potential exp(-2 d^2) over the distinct pairs of normalised rows
+    (one row: no pair, the mean of nothing is NaN and no gradient flows — torch.pdist's empty result)."""
+    x = torch.nn.functional.normalize(embedding, dim=-1)
+    sq = torch.pdist(x, p=2).square()
+    return torch.log(torch.exp(-2 * sq).mean())
