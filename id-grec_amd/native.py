@@ -109,6 +109,14 @@ PROTOTYPES = {
     "idg_align_uniform_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "idg_align_uniform_f32": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float,
                                         C.c_float, c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp]),
+    "idg_multinomial_nll_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "idg_multinomial_nll_f32": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp]),
+    "idg_vae_head_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "idg_vae_head_fwd_f32": (C.c_int, [c_vp, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, c_vp, C.c_float, C.c_uint64,
+                                       C.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "idg_vae_head_bwd_f32": (C.c_int, [c_vp, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, c_vp, C.c_float, C.c_uint64,
+                                       C.c_uint64, c_vp, c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp, c_vp]),
     "idg_infonce_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "idg_infonce_cross_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float, c_vp, c_vp,
                                         C.c_float, c_vp, c_vp]),
@@ -194,6 +202,7 @@ IDG_ADAM_DISCARD_GRAD = 2  # OR-ed into `accumulate` of idg_propagate_mean_bwd_a
 IDG_SSL_PLANNED = 2  # OR-ed into idg_infonce_pair_f32's `dedup`: the id lists are in the workspace already (idg_infonce_plan)
 IDG_BPR_TOUCHED_PRESET = 4  # OR-ed into `deterministic`: the touched bitmap already holds the batch's rows
 IDG_BPR_PLANNED = 2  # `deterministic` value: the sorted scatter plan is already in the workspace (idg_bpr_plan_f32)
+IDG_NLL_STATS_READY = 1  # idg_multinomial_nll_f32 flags: the row statistics in ws are current (the gradient pass only)
 IDG_GRAPH_SYMMETRIC = 1
 IDG_GRAPH_EXACT_ORDER = 2
 
@@ -246,7 +255,7 @@ except ImportError:  # host-only use (sampler / parser / adjacency) works withou
     _torch = None
 
 ACT_TANH, ACT_TANH_BWD = 1, 2  # idg_epilogue.act
-ABI_VERSION = 141  # include/idgrec.h IDG_VERSION the prototype table above was written against
+ABI_VERSION = 142  # include/idgrec.h IDG_VERSION the prototype table above was written against
 
 lib = C.CDLL(LIB_PATH)
 lib.idg_version.restype = C.c_int

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define IDG_VERSION 141 /* 0.5.2: idg_align_uniform_f32 / idg_align_uniform_workspace_bytes (DirectAU's alignment + uniformity loss); 0.5.1: idg_pack24_f32 / idg_unpack24_f32 / idg_reduce24_f32 / idg_alltoall_f32 (24-bit panel exchange, rank-ordered sum), idg_score_topk_candidate_counts, idg_score_topk_option (the top-K knobs: environment read once), idg_score_topk_info fills info[8], form 3's whole-call fall-back; idg_step_run_f32 takes next_ids_token; idg_step_synchronize also drains the side stream's preparations; 0.5.0: idg_step_* (one library call per training step), idg_adam_rows_f32; 0.4.4: IDG_ADAM_DISCARD_GRAD; 0.4.3: idg_event_synchronize; 0.4.2: idg_infonce_plan / IDG_SSL_PLANNED / idg_infonce_cross_ex_f32 (InfoNCE id lists a batch ahead); 0.4.1: idg_ngcf_layer_fwd_f32 / idg_ngcf_layer_bwd_f32 (one kernel per NGCF layer and direction); 0.4.0: idg_rows_layer_mean_n_f32 (any number of layers), idg_flags_compact_f32 (the touched-item
+#define IDG_VERSION 142 /* 0.5.3: idg_multinomial_nll_f32 / idg_multinomial_nll_workspace_bytes (CVGA's decoder: linear + log-softmax + multinomial NLL over the catalogue, forward and backward), idg_vae_head_fwd_f32 / idg_vae_head_bwd_f32 / idg_vae_head_workspace_bytes (its VAE head); 0.5.2: idg_align_uniform_f32 / idg_align_uniform_workspace_bytes (DirectAU's alignment + uniformity loss); 0.5.1: idg_pack24_f32 / idg_unpack24_f32 / idg_reduce24_f32 / idg_alltoall_f32 (24-bit panel exchange, rank-ordered sum), idg_score_topk_candidate_counts, idg_score_topk_option (the top-K knobs: environment read once), idg_score_topk_info fills info[8], form 3's whole-call fall-back; idg_step_run_f32 takes next_ids_token; idg_step_synchronize also drains the side stream's preparations; 0.5.0: idg_step_* (one library call per training step), idg_adam_rows_f32; 0.4.4: IDG_ADAM_DISCARD_GRAD; 0.4.3: idg_event_synchronize; 0.4.2: idg_infonce_plan / IDG_SSL_PLANNED / idg_infonce_cross_ex_f32 (InfoNCE id lists a batch ahead); 0.4.1: idg_ngcf_layer_fwd_f32 / idg_ngcf_layer_bwd_f32 (one kernel per NGCF layer and direction); 0.4.0: idg_rows_layer_mean_n_f32 (any number of layers), idg_flags_compact_f32 (the touched-item
                            agreement without a host read-back), idg_shard_prepare validates its geometry.
                            133 / 0.3.0: process-wide live-unit registry + idg_graph_live_units_check; idg_spmm_epi_f32 (every
                            epilogue option; out_rows and x_rows combined); round-3 sharded step: idg_rows_gather2 / _scatter /
@@ -639,6 +639,48 @@ int idg_align_uniform_f32(const float* final_panel, const float* ego_panel, int6
                           const int64_t* users, const int64_t* pos, int64_t B, int64_t num_users,
                           float gamma, float reg_lambda, float* loss, const float* upstream, float* g_final, float* g_ego,
                           int accumulate, const void* plan_ws, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * DEVICE: CVGA's decoder loss and VAE head (Zhang et al. TOIS'23; models/CVGA.py:40-85 and
+ * utility/utility_function/losses.py:53-56 of the reference), forward and backward.
+ *
+ * idg_multinomial_nll_f32: Z [B, d], W [I, d], c [I]; l_bi = <Z[b], W[i]> + c[i]; x_b = row users[b] of the train CSR
+ * (indptr int64 [U + 1], items int32 ascending per row, values fp32 — duplicate edges summed; DEVICE pointers, indexed by
+ * user id), n_b = sum_i x_bi:
+ *   loss[0] = (1 / B) sum_b (n_b log sum_i exp l_bi - sum_i x_bi l_bi)        (-mean(sum(log_softmax(l) * x, -1)))
+ * loss nullable.  gZ / gW / gc (all or none): d (up loss) / d Z, W, c with up = *upstream (DEVICE scalar; NULL = 1);
+ * gW and gc are WRITTEN for all I rows.  A user with an empty train row contributes 0 to both.  The [B, I] matrix is never
+ * stored: a statistics pass (row max and sum-exp over 64-item tiles in up to 256 chunks), then a gradient pass that
+ * recomputes each logit tile and forms both products and the column sums from it.  Logit tiles and products on the fp32
+ * matrix cores for d % 32 == 0, d <= 256, a SIMT form otherwise.  No float atomics, fixed summation orders: the same bits
+ * every run.  ws: idg_multinomial_nll_workspace_bytes (O(chunks B d + B)), 256-byte aligned; it also holds the row
+ * statistics: flags IDG_NLL_STATS_READY skips the statistics pass and reuses those of the last call on this ws with the
+ * same inputs (the backward of an autograd operator whose forward made them).
+ * ---------------------------------------------------------------------------------- */
+#define IDG_NLL_STATS_READY 1
+size_t idg_multinomial_nll_workspace_bytes(int64_t B, int64_t I, int64_t d);
+int idg_multinomial_nll_f32(const float* Z, const float* W, const float* c, int64_t B, int64_t I, int64_t d,
+                            const int64_t* users, const int64_t* indptr, const int32_t* items, const float* values,
+                            float* loss, const float* upstream, float* gZ, float* gW, float* gc, int flags, void* ws,
+                            void* stream);
+/* idg_vae_head_fwd_f32: row b of the encoder product is pre[(pre_rows ? pre_rows[b] : b) * ld_pre + 0 .. 2d):
+ *   h = keep * (pre_row + bias), mu = h[:d], logvar = h[d:], z[b] = eps * exp(logvar / 2) + mu                [B, d]
+ *   *kl = -0.5 / B^2 sum_b sum_j (1 + logvar - mu^2 - exp(logvar))                  (nullable; needs ws then)
+ * keep = 1 / (1 - p) or 0 (dropout p, NGCF's counter-based mask of idg_dropout.h over the 2d features of user users[b]);
+ * eps = eps_in[b, :] when given, else a standard normal from (seed, stream_id, users[b], feature).  eps_out [B, d] and
+ * keep_out [B, 2d] (nullable) receive what was used.  ws: idg_vae_head_workspace_bytes(B).
+ * idg_vae_head_bwd_f32: with the same (pre, users, bias, p, seed, stream_id, eps_in) — keep and eps are regenerated —
+ * gz = d L / d z (nullable: 0) and up = *upstream_kl (DEVICE scalar d L / d kl, NULL = 1):
+ *   gpre row (gpre_rows ? gpre_rows[b] : b) <- keep * (gz + up mu / B^2 | gz eps exp(logvar / 2) / 2 + up (exp(logvar) - 1) / 2B^2)
+ *   gbias (nullable) <- the column sums of those rows, in batch order.  With gpre_rows the rows must be distinct. */
+size_t idg_vae_head_workspace_bytes(int64_t B);
+int idg_vae_head_fwd_f32(const float* pre, int64_t ld_pre, const int64_t* pre_rows, const int64_t* users, int64_t B, int64_t d,
+                         const float* bias, float p, uint64_t seed, uint64_t stream_id, const float* eps_in, float* z,
+                         float* kl, float* eps_out, float* keep_out, void* ws, void* stream);
+int idg_vae_head_bwd_f32(const float* pre, int64_t ld_pre, const int64_t* pre_rows, const int64_t* users, int64_t B, int64_t d,
+                         const float* bias, float p, uint64_t seed, uint64_t stream_id, const float* eps_in, const float* gz,
+                         const float* upstream_kl, float* gpre, int64_t ld_gpre, const int64_t* gpre_rows, float* gbias,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------
  * DEVICE: dense Adam step  (torch.optim.Adam defaults, utility/utility_train/trainer.py:11,56:

@@ -134,6 +134,17 @@ class Data(object):
                                        torch.from_numpy(self._pos_indices).to(device))
         return self._device_cache[key]
 
+    def train_values_on(self, device):
+        """float32 [nnz] values of the train matrix in train_csr_on's entry order (duplicate train edges summed: 2) —
+        the interaction rows x of CVGA's likelihood (models/CVGA.py:130-134) without a dense [B, I] copy."""
+        import torch
+
+        key = "values:" + str(device)
+        if key not in self._device_cache:
+            vals = np.ascontiguousarray(self.user_item_net.data, dtype=np.float32)
+            self._device_cache[key] = torch.from_numpy(vals).to(device)
+        return self._device_cache[key]
+
     # ------------------------------------------------------------------ sparsity buckets
     def create_sparsity_split(self):
         """Four user groups of roughly equal interaction mass (data_loader.py:161-204)."""

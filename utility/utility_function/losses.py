@@ -5,7 +5,8 @@ reference and are plain torch expressions (they serve models that gather on thei
 NGCF-style encoders).  The LightGCN / MFBPR / SimGCL models do not come through here for
 their main loss: they call `idgrec_amd.ops.bpr_loss`, which fuses gather + both losses +
 gradients in one HIP kernel chain; DirectAU likewise calls `idgrec_amd.ops.align_uniform_loss`
-for its `get_align_loss` / `get_uniform_loss` terms.
+for its `get_align_loss` / `get_uniform_loss` terms, and CVGA `idgrec_amd.ops.multinomial_nll` /
+`vae_head` for the two terms of `get_ELBO_loss`.
 """
 import torch
 
@@ -55,3 +56,11 @@ def get_uniform_loss(embedding):
     x = torch.nn.functional.normalize(embedding, dim=-1)
     sq = torch.pdist(x, p=2).square()
     return torch.log(torch.exp(-2 * sq).mean())
+
+
+def get_ELBO_loss(recon_x, x, mu, logvar, anneal):
+    """CVGA's ELBO pair: the multinomial NLL -mean_b sum_i log_softmax(recon_x)_bi x_bi and anneal times the KL term
+    -0.5 / B * mean_b sum_j (1 + logvar - mu^2 - exp logvar) — B in front of a mean, so divided by B twice."""
+    BCE = - torch.mean(torch.sum(torch.nn.functional.log_softmax(recon_x, 1) * x, -1))
+    KLD = - 0.5 / recon_x.size(0) * torch.mean(torch.sum(1 + logvar - mu.pow(2) - logvar.exp(), dim=1))
+    return BCE, anneal * KLD
