@@ -117,6 +117,9 @@ PROTOTYPES = {
                                        C.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "idg_vae_head_bwd_f32": (C.c_int, [c_vp, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, c_vp, C.c_float, C.c_uint64,
                                        C.c_uint64, c_vp, c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp, c_vp]),
+    "idg_table_nce_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int]),
+    "idg_table_nce_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(c_vp), C.POINTER(c_vp), C.c_int64,
+                                    c_vp, c_f32p, C.c_float, c_vp, c_vp, c_vp, C.POINTER(c_vp), c_vp, c_vp]),
     "idg_infonce_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "idg_infonce_cross_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float, c_vp, c_vp,
                                         C.c_float, c_vp, c_vp]),
@@ -203,6 +206,7 @@ IDG_SSL_PLANNED = 2  # OR-ed into idg_infonce_pair_f32's `dedup`: the id lists a
 IDG_BPR_TOUCHED_PRESET = 4  # OR-ed into `deterministic`: the touched bitmap already holds the batch's rows
 IDG_BPR_PLANNED = 2  # `deterministic` value: the sorted scatter plan is already in the workspace (idg_bpr_plan_f32)
 IDG_NLL_STATS_READY = 1  # idg_multinomial_nll_f32 flags: the row statistics in ws are current (the gradient pass only)
+IDG_TNCE_MAX_QUERY_BLOCKS = 4  # idg_table_nce_f32: query blocks one call takes
 IDG_GRAPH_SYMMETRIC = 1
 IDG_GRAPH_EXACT_ORDER = 2
 

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define IDG_VERSION 142 /* 0.5.3: idg_multinomial_nll_f32 / idg_multinomial_nll_workspace_bytes (CVGA's decoder: linear + log-softmax + multinomial NLL over the catalogue, forward and backward), idg_vae_head_fwd_f32 / idg_vae_head_bwd_f32 / idg_vae_head_workspace_bytes (its VAE head); 0.5.2: idg_align_uniform_f32 / idg_align_uniform_workspace_bytes (DirectAU's alignment + uniformity loss); 0.5.1: idg_pack24_f32 / idg_unpack24_f32 / idg_reduce24_f32 / idg_alltoall_f32 (24-bit panel exchange, rank-ordered sum), idg_score_topk_candidate_counts, idg_score_topk_option (the top-K knobs: environment read once), idg_score_topk_info fills info[8], form 3's whole-call fall-back; idg_step_run_f32 takes next_ids_token; idg_step_synchronize also drains the side stream's preparations; 0.5.0: idg_step_* (one library call per training step), idg_adam_rows_f32; 0.4.4: IDG_ADAM_DISCARD_GRAD; 0.4.3: idg_event_synchronize; 0.4.2: idg_infonce_plan / IDG_SSL_PLANNED / idg_infonce_cross_ex_f32 (InfoNCE id lists a batch ahead); 0.4.1: idg_ngcf_layer_fwd_f32 / idg_ngcf_layer_bwd_f32 (one kernel per NGCF layer and direction); 0.4.0: idg_rows_layer_mean_n_f32 (any number of layers), idg_flags_compact_f32 (the touched-item
+#define IDG_VERSION 142 /* 0.5.3 (added since, no entry point changed, so the number stays): idg_table_nce_f32 / idg_table_nce_workspace_bytes (CGCL's full-table contrastive loss: every batch row against a whole normalised embedding table, forward and backward); 0.5.3: idg_multinomial_nll_f32 / idg_multinomial_nll_workspace_bytes (CVGA's decoder: linear + log-softmax + multinomial NLL over the catalogue, forward and backward), idg_vae_head_fwd_f32 / idg_vae_head_bwd_f32 / idg_vae_head_workspace_bytes (its VAE head); 0.5.2: idg_align_uniform_f32 / idg_align_uniform_workspace_bytes (DirectAU's alignment + uniformity loss); 0.5.1: idg_pack24_f32 / idg_unpack24_f32 / idg_reduce24_f32 / idg_alltoall_f32 (24-bit panel exchange, rank-ordered sum), idg_score_topk_candidate_counts, idg_score_topk_option (the top-K knobs: environment read once), idg_score_topk_info fills info[8], form 3's whole-call fall-back; idg_step_run_f32 takes next_ids_token; idg_step_synchronize also drains the side stream's preparations; 0.5.0: idg_step_* (one library call per training step), idg_adam_rows_f32; 0.4.4: IDG_ADAM_DISCARD_GRAD; 0.4.3: idg_event_synchronize; 0.4.2: idg_infonce_plan / IDG_SSL_PLANNED / idg_infonce_cross_ex_f32 (InfoNCE id lists a batch ahead); 0.4.1: idg_ngcf_layer_fwd_f32 / idg_ngcf_layer_bwd_f32 (one kernel per NGCF layer and direction); 0.4.0: idg_rows_layer_mean_n_f32 (any number of layers), idg_flags_compact_f32 (the touched-item
                            agreement without a host read-back), idg_shard_prepare validates its geometry.
                            133 / 0.3.0: process-wide live-unit registry + idg_graph_live_units_check; idg_spmm_epi_f32 (every
                            epilogue option; out_rows and x_rows combined); round-3 sharded step: idg_rows_gather2 / _scatter /
@@ -681,6 +681,36 @@ int idg_vae_head_bwd_f32(const float* pre, int64_t ld_pre, const int64_t* pre_ro
                          const float* bias, float p, uint64_t seed, uint64_t stream_id, const float* eps_in, const float* gz,
                          const float* upstream_kl, float* gpre, int64_t ld_gpre, const int64_t* gpre_rows, float* gbias,
                          void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * DEVICE: full-table contrastive loss (CGCL, He et al. SIGIR'23; models/CGCL.py:95-215 of the reference, the expression of
+ * utility/utility_function/losses.py:38-50), forward and backward.
+ *
+ * Table: rows [row0, row0 + N) of table_panel [*, d], each divided by max(||x||, 1e-12) (F.normalize) -> Th.  nq query
+ * blocks (1 .. IDG_TNCE_MAX_QUERY_BLOCKS) share it: block k is the B rows query_panels[k][query_ids[k][b]] (row stride d;
+ * any panel, ids may repeat), normalised the same way -> Qh_k.  The positive of query b is table row pos_ids[b] in [0, N)
+ * (one list for the call; the caller's contract, as the query ids are).  query_panels / query_ids / g_query_panels / weights
+ * are HOST arrays of nq entries; the id lists and panels they name are DEVICE memory.  With s_bj = <Qh_b, Th_j>:
+ *   loss[k] = -weights[k] sum_b log( exp(s_b,pos(b) / tau) / sum_{j < N} exp(s_bj / tau) + 1e-7 )
+ * loss [nq] nullable.  g_table_panel and g_query_panels (all or none): the gradients of sum_k up[k] loss[k] (upstream: DEVICE
+ * [nq], NULL = ones) are ADDED into rows [row0, row0 + N) of g_table_panel (all N rows: the term is dense) and into rows
+ * query_ids[k][b] of g_query_panels[k] (repeated ids summed in batch order), both back through the normalisation.  Buffers
+ * may coincide (one panel as table and as query panel, one gradient panel for several roles): the additions are made one
+ * launch after the other.
+ * Scores are cosines, so exp((s - 1) / tau) is used in place of exp(s / tau): the common factor cancels in the ratio, no
+ * running maximum is needed and the sums stay finite for any tau > 0, where the reference's exp(1 / tau) overflows fp32
+ * for tau below about 0.0113.  The [B, N] matrix is never stored: 128 x 128 score tiles are formed twice (a batch-major pass
+ * for the row sums and d Qh, a table-major pass for d Th) on the fp32 matrix cores (v_mfma_f32_32x32x2_f32; the operands are
+ * zero-padded to a multiple of 32 columns, so every d <= 256 takes that path).  No float atomics, fixed summation orders:
+ * the same bits every run.  ws: idg_table_nce_workspace_bytes (the normalised copies, per-row statistics, and ordered
+ * partial sums: O((N + chunks nq B) d), chunks <= 64), 256-byte aligned; 0 is returned for sizes that are not built.
+ * ---------------------------------------------------------------------------------- */
+#define IDG_TNCE_MAX_QUERY_BLOCKS 4
+size_t idg_table_nce_workspace_bytes(int64_t B, int64_t N, int64_t d, int nq);
+int idg_table_nce_f32(const float* table_panel, int64_t row0, int64_t N, int64_t d, int nq,
+                      const float* const* query_panels, const int64_t* const* query_ids, int64_t B,
+                      const int64_t* pos_ids, const float* weights, float temperature, float* loss,
+                      const float* upstream, float* g_table_panel, float* const* g_query_panels, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * DEVICE: dense Adam step  (torch.optim.Adam defaults, utility/utility_train/trainer.py:11,56:
