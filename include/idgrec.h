@@ -713,6 +713,35 @@ int idg_table_nce_f32(const float* table_panel, int64_t row0, int64_t N, int64_t
                       const float* upstream, float* g_table_panel, float* const* g_query_panels, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * DEVICE: Lloyd's k-means, the E-step of NCL (Lin et al. WWW'22; models/NCL.py:66-81 of the reference: faiss.Kmeans on a
+ * host copy of each embedding table, then index.search(x, 1) for the final assignment).
+ *
+ * X: N rows of d floats, row stride ldx >= d (a panel may be wider than the rows used).  C: [K, d], contiguous.
+ * idg_kmeans_assign_f32: assign[i] = argmin_j ||x_i - c_j||^2, evaluated as ||c_j||^2 - 2 <x_i, c_j>, ties to the lowest j;
+ *   dist2 (nullable [N]): max(0, ||x_i||^2 + that minimum).  The products run on the fp32 matrix cores
+ *   (v_mfma_f32_32x32x2_f32; the operands are zero-padded to a multiple of 32 columns, so every d <= 256 takes one path) in
+ *   128 x 128 tiles; the running (min, arg-min) pair stays in registers across the centroid tiles and the [N, K] matrix is
+ *   never stored.  With few row tiles K is split over workgroups and the partial minima are combined in chunk order.
+ * idg_kmeans_update_f32: C[j] <- the mean of the rows with assign[i] = j, the rows added in ascending row order (brought
+ *   together by a stable counting sort of the row ids; integer atomics in its histogram only); counts (nullable [K]): the
+ *   rows per cluster.  A cluster without rows keeps the centroid it had, bit for bit (faiss splits its largest cluster
+ *   instead: DESIGN.md).  An index outside [0, K) is ignored.
+ * idg_kmeans_f32: niter x (assign, update) from the centroids in C, then one more assign against the final centroids;
+ *   inertia (nullable [niter + 1]): the sum of dist2 of every assign, the last entry the final one.  Launches on one stream,
+ *   no host read-back.
+ * No float atomics, fixed summation orders: the same bits every run.  ws: idg_kmeans_workspace_bytes (the padded copies,
+ * per-chunk minima and the sorted row ids: O((N + K) d + chunks N), chunks <= 64), 256-byte aligned; 0 is returned for sizes
+ * that are not built (d > 256, N or K outside int32).
+ * ---------------------------------------------------------------------------------- */
+size_t idg_kmeans_workspace_bytes(int64_t N, int64_t K, int64_t d);
+int idg_kmeans_assign_f32(const float* X, int64_t ldx, int64_t N, int64_t d, const float* C, int64_t K, int32_t* assign,
+                          float* dist2, void* ws, void* stream);
+int idg_kmeans_update_f32(const float* X, int64_t ldx, int64_t N, int64_t d, const int32_t* assign, int64_t K, float* C,
+                          int32_t* counts, void* ws, void* stream);
+int idg_kmeans_f32(const float* X, int64_t ldx, int64_t N, int64_t d, int64_t K, int niter, float* C, int32_t* assign,
+                   float* inertia, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * DEVICE: dense Adam step  (torch.optim.Adam defaults, utility/utility_train/trainer.py:11,56:
  * betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad).  step is 1-based.  The
  * hyper-parameters are doubles because torch forms lr/(1-beta1^t) and sqrt(1-beta2^t) in

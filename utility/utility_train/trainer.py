@@ -58,6 +58,7 @@ def universal_trainer(model, args, config, dataset, device, logger):
         print('-' * 100)
         start_time = time()
         model.train()
+        getattr(model, "begin_epoch", lambda e: None)(epoch)  # per-epoch work of a model that has some (NCL's E-step)
 
         users, pos_items, neg_items = lookahead if lookahead is not None else draw_epoch()
         lookahead = None
