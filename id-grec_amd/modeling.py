@@ -14,6 +14,17 @@ from . import ops
 from .engine import PropagationEngine
 
 
+def adam_group_over(optimizer, params):
+    """The single param group of `optimizer` when it is an idgrec_amd.ops.Adam over exactly `params` (the same tensors in
+    the same order): the gate of every fused_train_step.  None otherwise."""
+    if not isinstance(optimizer, ops.Adam) or len(optimizer.param_groups) != 1:
+        return None
+    group = optimizer.param_groups[0]
+    if len(group["params"]) != len(params) or any(a is not b for a, b in zip(group["params"], params)):
+        return None
+    return group
+
+
 class _PackedPanel(torch.autograd.Function):
     """(user_weight, item_weight) -> the [n, d] panel they both live in, without copying."""
 
@@ -132,18 +143,17 @@ class PackedRecommender(nn.Module):
         self.item_embedding.weight.grad = eng.grad[U:]
         return loss
 
-    def fused_train_step(self, users, pos, neg, loss_out, optimizer):
-        """forward + backward + optimizer.step() as ONE chain of kernels (Adam is applied in the epilogue of the
-        last backward product).  Returns False — nothing done — unless `optimizer` is an idgrec_amd.ops.Adam over
-        exactly this model's two packed tables; its state (step, exp_avg, exp_avg_sq) stays the single source of
-        truth: the moments are re-homed once into packed [n, d] panels that the state entries then view."""
+    def _packed_adam(self, optimizer):
+        """The hand-off of a fused step to `optimizer`: (param group, user state, item state, (exp_avg, exp_avg_sq) panels),
+        or None — nothing done — unless it is an idgrec_amd.ops.Adam over exactly this model's two packed tables whose two
+        step counters agree.  Its state (step, exp_avg, exp_avg_sq) stays the single source of truth: the moments are
+        re-homed once into packed [n, d] panels that the state entries then view."""
         uw, iw = self.user_embedding.weight, self.item_embedding.weight
-        if not isinstance(optimizer, ops.Adam) or len(optimizer.param_groups) != 1:
-            return False
-        group = optimizer.param_groups[0]
-        if len(group["params"]) != 2 or group["params"][0] is not uw or group["params"][1] is not iw:
-            return False
-        eng = self.engine()
+        group = adam_group_over(optimizer, [uw, iw])
+        if group is None:
+            return None
+        if not self._is_packed():
+            self._pack()
         U = self.dataset.num_users
         st_u, st_i = optimizer.state[uw], optimizer.state[iw]
         packed = getattr(self, "_packed_moments", None)
@@ -158,7 +168,20 @@ class PackedRecommender(nn.Module):
                 st["exp_avg"], st["exp_avg_sq"] = m[sl], v[sl]
             packed = self._packed_moments = (m, v)
         if st_u["step"] != st_i["step"]:
+            return None
+        return group, st_u, st_i, packed
+
+    def fused_train_step(self, users, pos, neg, loss_out, optimizer):
+        """forward + backward + optimizer.step() as ONE chain of kernels (Adam is applied in the epilogue of the
+        last backward product), in the state of `optimizer` as _packed_adam hands it over.  Returns False — nothing
+        done — when it does not."""
+        adam = self._packed_adam(optimizer)
+        if adam is None:
             return False
+        group, st_u, st_i, packed = adam
+        uw, iw = self.user_embedding.weight, self.item_embedding.weight
+        U = self.dataset.num_users
+        eng = self.engine()
         eng.exp_avg, eng.exp_avg_sq = packed
         eng.lr, eng.betas, eng.eps = float(group["lr"]), tuple(group["betas"]), float(group["eps"])
         eng.step_count = int(st_u["step"])
@@ -222,3 +245,110 @@ class PackedRecommender(nn.Module):
                 rating[rows, cols] = -1
                 out.append(torch.topk(rating, k=k)[1])
             return torch.cat(out)
+
+
+class LayerChainRecommender(PackedRecommender):
+    """LightGCN mean + BPR + contrastive terms that read individual layers' outputs and whose gradients reach every row of
+    both tables (CGCL, NCL).  The fused step keeps every layer: K products with the running layer sum in their epilogue, the
+    fused BPR on the mean, the subclass's contrastive calls adding into one gradient panel per layer they read, the backward
+    chain g_k = A g_(k+1) + g_mean / (K + 1) + g_ssl_k, and a dense Adam step of the packed panel.  A subclass sets n_layers,
+    attaches the graph and states `ssl_layers`, `ssl_parts` and `_ssl_raw`."""
+    supports_fused_step = True
+    #: the layers whose output carries a contrastive gradient panel; layer 0 is always one (the regulariser's gradient lands there)
+    ssl_layers = None
+    #: shape of the zeroed float32 scratch _ssl_raw's calls write their loss terms to
+    ssl_parts = None
+    _buf = None
+
+    def _ssl_raw(self, E, G, users, pos, parts, loss_out):
+        """Issue the contrastive calls: E = [E0, .., EK], G = {layer: its gradient panel, added into}, parts = the zeroed
+        scratch; writes loss_out[2:]."""
+        raise NotImplementedError
+
+    def _layers(self):
+        """([E0, E1, .., EK], their mean [n, d])."""
+        layers = [self.ego_panel()]
+        for _ in range(self.n_layers):
+            layers.append(ops.spmm(self.Graph, layers[-1]))
+        return layers, torch.stack(layers, dim=1).mean(dim=1)
+
+    def aggregate(self):
+        """(users [U,d], items [I,d], [E0, E1, .., EK]): the layer mean and every layer's output."""
+        layers, final = self._layers()
+        users, items = torch.split(final, [self.dataset.num_users, self.dataset.num_items])
+        return users, items, layers
+
+    def _step_buffers(self):
+        st = self._storage
+        if self._buf is None or self._buf["key"] != (st.data_ptr(), st.device):
+            K = self.n_layers
+            new = lambda: torch.empty_like(st)  # noqa: E731
+            self._buf = dict(key=(st.data_ptr(), st.device), E=[None] + [new() for _ in range(K)], S=new(), final=new(),
+                             g_final=new(), G={k: new() for k in self.ssl_layers}, chain=[new(), new()], grad=None,
+                             parts=torch.empty(self.ssl_parts, dtype=torch.float32, device=st.device))
+        return self._buf
+
+    def fused_loss_and_grad(self, users, pos, neg, loss_out=None):
+        """The n_fused_losses losses (device tensor) and d(sum) / d(weights) in the two parameters' .grad, as one fixed chain
+        of library calls."""
+        if not self._is_packed():
+            self._pack()
+        st = self._storage
+        U, K = self.dataset.num_users, self.n_layers
+        users, pos, neg = (t.long().contiguous() for t in (users, pos, neg))
+        buf = self._step_buffers()
+        self._eval_cache = None
+        if loss_out is None:
+            loss_out = torch.empty(self.n_fused_losses, dtype=torch.float32, device=st.device)
+        E, G = buf["E"], buf["G"]
+        E[0] = st
+        # layers 1..K and their mean: the running sum rides in the product's epilogue
+        for k in range(1, K + 1):
+            last = k == K
+            ops.spmm_ex_raw(self.Graph, E[k - 1], Y=E[k], sum_in=E[0] if k == 1 else buf["S"],
+                            sum_out=buf["final"] if last else buf["S"], div=float(K + 1) if last else 1.0)
+        for t in (buf["g_final"], *G.values()):
+            t.zero_()
+        # BPR on the mean; the regulariser's gradient lands with layer 0's
+        ops.bpr_fused_raw(buf["final"], st, users, pos, neg, U, self.reg_lambda, buf["g_final"], G[0], loss=loss_out[0:2])
+        self._ssl_raw(E, G, users, pos, buf["parts"].zero_(), loss_out)
+        # g_k = A g_(k+1) + g_final / (K + 1) + g_ssl_k, from the last layer down (g_ssl_k = 0 for a layer without a panel)
+        share = 1.0 / (K + 1)
+        cur = buf["chain"][K % 2]
+        if K in G:
+            ops.lincomb_raw(cur, G[K], 1.0, buf["g_final"], share)
+        else:
+            ops.lincomb_raw(cur, buf["g_final"], share)
+        for k in range(K - 1, -1, -1):
+            if k in G:
+                add = G[k]
+                ops.lincomb_raw(add, add, 1.0, buf["g_final"], share)
+            else:
+                add = buf["S"]
+                ops.lincomb_raw(add, buf["g_final"], share)
+            nxt = buf["chain"][k % 2]
+            self.Graph.spmm_raw(cur, addend=add, out=nxt)
+            cur = nxt
+        buf["grad"] = cur
+        self.user_embedding.weight.grad = cur[:U]
+        self.item_embedding.weight.grad = cur[U:]
+        return loss_out
+
+    def fused_train_step(self, users, pos, neg, loss_out, optimizer):
+        """fused_loss_and_grad + the dense Adam step of the packed panel (the table gradients reach every row), in the state
+        of `optimizer` as _packed_adam hands it over.  False — nothing done — when it does not."""
+        adam = self._packed_adam(optimizer)
+        if adam is None:
+            return False
+        group, st_u, st_i, (m, v) = adam
+        self.fused_loss_and_grad(users, pos, neg, loss_out)
+        step = int(st_u["step"]) + 1
+        b1, b2 = group["betas"]
+        ops.adam_step_raw(self._storage, self._buf["grad"], m, v, group["lr"], step, b1, b2, group["eps"])
+        st_u["step"] = st_i["step"] = step
+        if not getattr(self, "keep_fused_grad", False):
+            self.user_embedding.weight.grad = self.item_embedding.weight.grad = None
+        return True
+
+    def prefetch_batch(self, users, pos, neg):
+        """Nothing to prepare ahead: the step's index work is inside its calls."""

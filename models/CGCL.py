@@ -12,22 +12,20 @@ that share a table going into one call:
     E1 users   E2 items[pos]  (struct, ssl_lambda_gamma gamma)                                                        user
     E1 items   E2 users[user] (struct, .. (1 - gamma))                                                                pos
 
-The fused step runs the same chain without autograd: K products keeping every layer, the fused BPR on the layer mean, the
-four calls adding into per-layer gradient panels, the backward chain g_k = A g_(k+1) + g_mean / (K + 1) + g_ssl_k, and a
-dense Adam step (the table gradients reach every row).
+The fused step is LayerChainRecommender's (idgrec_amd/modeling.py: every layer kept, the fused BPR on the layer mean, the
+backward chain, a dense Adam step); CGCL states that layers 0, 1 and 2 carry a gradient panel and issues the four calls.
 """
-import torch
-
 import utility.utility_data.data_graph as data_graph
 import utility.utility_train.trainer as trainer
 from idgrec_amd import ops
-from idgrec_amd.modeling import PackedRecommender
+from idgrec_amd.modeling import LayerChainRecommender
 
 
-class CGCL(PackedRecommender):
+class CGCL(LayerChainRecommender):
     include_layer0 = True  # E0 takes part in the layer mean (models/CGCL.py:44-60)
-    supports_fused_step = True
     n_fused_losses = 5
+    ssl_layers = (0, 1, 2)  # center, candidate, context: layers above 2 carry no contrastive term
+    ssl_parts = (4, 2)  # one row per call of _terms(), one entry per query block
 
     def __init__(self, config, dataset, device):
         super(CGCL, self).__init__(config, dataset, device)
@@ -43,22 +41,8 @@ class CGCL(PackedRecommender):
             raise ValueError("CGCL needs GCN_layer >= 2: its contrastive terms compare the outputs of layers 0, 1 and 2 "
                              "(got GCN_layer = %d)" % self.n_layers)
         self.attach_graph(data_graph.sparse_adjacency_matrix(dataset))
-        self._buf = None
 
     # ------------------------------------------------------------------ the reference's surface
-    def _layers(self):
-        """([E0, E1, .., EK], their mean [n, d])."""
-        layers = [self.ego_panel()]
-        for _ in range(self.n_layers):
-            layers.append(ops.spmm(self.Graph, layers[-1]))
-        return layers, torch.stack(layers, dim=1).mean(dim=1)
-
-    def aggregate(self):
-        """(users [U,d], items [I,d], [E0, E1, .., EK]): the layer mean and every layer's output (models/CGCL.py:44-60)."""
-        layers, final = self._layers()
-        users, items = torch.split(final, [self.dataset.num_users, self.dataset.num_items])
-        return users, items, layers
-
     def _terms(self):
         """The four calls: (table layer, row0, N, [(query layer, weight, slot of the loss triple)], the table is the users')."""
         U, I = self.dataset.num_users, self.dataset.num_items
@@ -86,42 +70,9 @@ class CGCL(PackedRecommender):
                 ssl[slot] = ssl[slot] + term
         return [bpr_loss, reg_loss] + ssl
 
-    # ------------------------------------------------------------------ fused, autograd-free step
-    def _step_buffers(self):
-        st = self._storage
-        if self._buf is None or self._buf["key"] != (st.data_ptr(), st.device):
-            K = self.n_layers
-            new = lambda: torch.empty_like(st)  # noqa: E731
-            self._buf = dict(key=(st.data_ptr(), st.device), E=[None] + [new() for _ in range(K)], S=new(), final=new(),
-                             g_final=new(), G=[new() for _ in range(3)], chain=[new(), new()], grad=None,
-                             parts=torch.empty((4, 2), dtype=torch.float32, device=st.device))
-        return self._buf
-
-    def fused_loss_and_grad(self, users, pos, neg, loss_out=None):
-        """The five losses (device tensor) and d(sum) / d(weights) in the two parameters' .grad, as one fixed chain of library
-        calls."""
-        if not self._is_packed():
-            self._pack()
-        st = self._storage
-        U, K = self.dataset.num_users, self.n_layers
-        users, pos, neg = (t.long().contiguous() for t in (users, pos, neg))
-        buf = self._step_buffers()
-        self._eval_cache = None
-        if loss_out is None:
-            loss_out = torch.empty(5, dtype=torch.float32, device=st.device)
-        E, G = buf["E"], buf["G"]
-        E[0] = st
-        # layers 1..K and their mean: the running sum rides in the product's epilogue
-        for k in range(1, K + 1):
-            last = k == K
-            ops.spmm_ex_raw(self.Graph, E[k - 1], Y=E[k], sum_in=E[0] if k == 1 else buf["S"],
-                            sum_out=buf["final"] if last else buf["S"], div=float(K + 1) if last else 1.0)
-        for t in (buf["g_final"], G[0], G[1], G[2]):
-            t.zero_()
-        # BPR on the mean; the regulariser's gradient lands with layer 0's
-        ops.bpr_fused_raw(buf["final"], st, users, pos, neg, U, self.reg_lambda, buf["g_final"], G[0], loss=loss_out[0:2])
-        item_rows = pos + U
-        parts = buf["parts"].zero_()
+    # ------------------------------------------------------------------ fused step: the hook of LayerChainRecommender
+    def _ssl_raw(self, E, G, users, pos, parts, loss_out):
+        item_rows = pos + self.dataset.num_users
         for c, (tl, row0, N, blocks, user_side) in enumerate(self._terms()):
             q_ids = item_rows if user_side else users
             ops.table_nce_raw(E[tl], row0, N, [E[ql] for ql, _, _ in blocks], [q_ids] * len(blocks),
@@ -129,66 +80,6 @@ class CGCL(PackedRecommender):
                               loss=parts[c, :len(blocks)], g_table=G[tl], g_queries=[G[ql] for ql, _, _ in blocks])
         loss_out[2:4] = parts[0] + parts[1]
         loss_out[4] = parts[2, 0] + parts[3, 0]
-        # g_k = A g_(k+1) + g_final / (K + 1) + g_ssl_k, from the last layer down (layers above 2 carry no contrastive term)
-        share = 1.0 / (K + 1)
-        cur = buf["chain"][K % 2]
-        if K >= 3:
-            ops.lincomb_raw(cur, buf["g_final"], share)
-        else:
-            ops.lincomb_raw(cur, G[2], 1.0, buf["g_final"], share)
-        for k in range(K - 1, -1, -1):
-            if k <= 2:
-                add = G[k]
-                ops.lincomb_raw(add, G[k], 1.0, buf["g_final"], share)
-            else:
-                add = buf["S"]
-                ops.lincomb_raw(add, buf["g_final"], share)
-            nxt = buf["chain"][k % 2]
-            self.Graph.spmm_raw(cur, addend=add, out=nxt)
-            cur = nxt
-        buf["grad"] = cur
-        self.user_embedding.weight.grad = cur[:U]
-        self.item_embedding.weight.grad = cur[U:]
-        return loss_out
-
-    def fused_train_step(self, users, pos, neg, loss_out, optimizer):
-        """fused_loss_and_grad + the dense Adam step of the packed panel, in the state of `optimizer` (an ops.Adam over exactly
-        the two tables; its step / exp_avg / exp_avg_sq stay the single source of truth, the moments re-homed once into
-        packed [n, d] panels that the state entries view, as in PackedRecommender).  False — nothing done — otherwise."""
-        uw, iw = self.user_embedding.weight, self.item_embedding.weight
-        if not isinstance(optimizer, ops.Adam) or len(optimizer.param_groups) != 1:
-            return False
-        group = optimizer.param_groups[0]
-        if len(group["params"]) != 2 or group["params"][0] is not uw or group["params"][1] is not iw:
-            return False
-        if not self._is_packed():
-            self._pack()
-        U = self.dataset.num_users
-        st_u, st_i = optimizer.state[uw], optimizer.state[iw]
-        packed = getattr(self, "_packed_moments", None)
-        if (packed is None or packed[0].device != self._storage.device or not st_u or not st_i
-                or st_u["exp_avg"].data_ptr() != packed[0].data_ptr() or st_i["exp_avg_sq"].data_ptr() != packed[1][U:].data_ptr()):
-            m, v = torch.zeros_like(self._storage), torch.zeros_like(self._storage)
-            for st, sl in ((st_u, slice(0, U)), (st_i, slice(U, None))):
-                if st:  # the optimizer has already stepped the other way: keep what it accumulated
-                    m[sl].copy_(st["exp_avg"])
-                    v[sl].copy_(st["exp_avg_sq"])
-                st.setdefault("step", 0)
-                st["exp_avg"], st["exp_avg_sq"] = m[sl], v[sl]
-            packed = self._packed_moments = (m, v)
-        if st_u["step"] != st_i["step"]:
-            return False
-        self.fused_loss_and_grad(users, pos, neg, loss_out)
-        step = int(st_u["step"]) + 1
-        b1, b2 = group["betas"]
-        ops.adam_step_raw(self._storage, self._buf["grad"], packed[0], packed[1], group["lr"], step, b1, b2, group["eps"])
-        st_u["step"] = st_i["step"] = step
-        if not getattr(self, "keep_fused_grad", False):
-            uw.grad = iw.grad = None
-        return True
-
-    def prefetch_batch(self, users, pos, neg):
-        """Nothing to prepare ahead: the step's index work is inside its calls."""
 
 
 class Trainer():

@@ -20,6 +20,7 @@ import utility.utility_function.tools as tools
 import utility.utility_train.trainer as trainer
 from idgrec_amd import ops
 from idgrec_amd.egcf import EgcfAltEngine, EgcfEngine
+from idgrec_amd.modeling import adam_group_over
 
 
 class EGCF(nn.Module):
@@ -86,10 +87,8 @@ class EGCF(nn.Module):
         """forward + backward + Adam as ONE chain of kernels; False (nothing done) unless `optimizer` is an
         idgrec_amd.ops.Adam over exactly the item table.  The optimizer's state stays the single source of truth."""
         w = self.item_embedding.weight
-        if not isinstance(optimizer, ops.Adam) or len(optimizer.param_groups) != 1:
-            return False
-        group = optimizer.param_groups[0]
-        if len(group["params"]) != 1 or group["params"][0] is not w:
+        group = adam_group_over(optimizer, [w])
+        if group is None:
             return False
         eng = self.engine()
         st = optimizer.state[w]

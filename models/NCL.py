@@ -13,22 +13,22 @@ The centroids come from the E-step: from epoch `proto_warmup` on (the reference'
 at the top of every epoch.  The reference copies them to the host for faiss.Kmeans; here ops.kmeans / idg_kmeans_f32 runs
 Lloyd's iterations on the device, on the packed panel in place (DESIGN.md §4 lists the deviations from faiss).
 
-The fused step runs the same chain without autograd: K products keeping layer 2 * cl_layer and the running mean, the fused
-BPR, the two full-table calls and the prototype call adding into the gradient panels of layers 0 and 2 * cl_layer, the
-backward chain g_k = A g_(k+1) + g_mean / (K + 1) + g_ssl_k, and a dense Adam step.
+The fused step is LayerChainRecommender's (idgrec_amd/modeling.py: every layer kept, the fused BPR on the layer mean, the
+backward chain, a dense Adam step); NCL states that layers 0 and 2 * cl_layer carry a gradient panel and issues the two
+full-table calls and, after the warm-up, the prototype call.
 """
 import torch
 
 import utility.utility_data.data_graph as data_graph
 import utility.utility_train.trainer as trainer
 from idgrec_amd import ops
-from idgrec_amd.modeling import PackedRecommender
+from idgrec_amd.modeling import LayerChainRecommender
 
 
-class NCL(PackedRecommender):
+class NCL(LayerChainRecommender):
     include_layer0 = True  # E0 takes part in the layer mean (models/NCL.py:48-64)
-    supports_fused_step = True
     n_fused_losses = 4  # [bpr, reg, ssl, proto]; the prototype column is 0 before the warm-up ends
+    ssl_parts = (4,)  # structure users, structure items, the prototype call's pair
 
     def __init__(self, config, dataset, device):
         super(NCL, self).__init__(config, dataset, device)
@@ -38,6 +38,7 @@ class NCL(PackedRecommender):
         self.alpha = float(config['alpha'])
         self.temperature = float(config['temperature'])
         self.cl_layer = int(config['cl_layer'])
+        self.ssl_layers = (0, 2 * self.cl_layer)  # only E0 and the structural term's layer carry a contrastive term
         self.batch_size = int(config['batch_size'])
         self.proto_warmup = int(config.get('proto_warmup', 20))  # models/NCL.py:110,177: `epoch < 20`
         self.kmeans_niter = int(config.get('kmeans_niter', 25))  # faiss.Kmeans' default niter
@@ -53,22 +54,8 @@ class NCL(PackedRecommender):
         self.epoch = 0
         self.user_centroids = self.user_2cluster = self.item_centroids = self.item_2cluster = None
         self._proto = None
-        self._buf = None
 
     # ------------------------------------------------------------------ the reference's surface
-    def _layers(self):
-        """([E0, E1, .., EK], their mean [n, d])."""
-        layers = [self.ego_panel()]
-        for _ in range(self.n_layers):
-            layers.append(ops.spmm(self.Graph, layers[-1]))
-        return layers, torch.stack(layers, dim=1).mean(dim=1)
-
-    def aggregate(self):
-        """(users [U,d], items [I,d], [E0, E1, .., EK]) (models/NCL.py:48-64)."""
-        layers, final = self._layers()
-        users, items = torch.split(final, [self.dataset.num_users, self.dataset.num_items])
-        return users, items, layers
-
     def E_step(self):
         """k-means of the user rows and of the item rows of the packed ego panel, on the device (models/NCL.py:66-81)."""
         if not self._is_packed():
@@ -123,41 +110,11 @@ class NCL(PackedRecommender):
         loss_list.append(self.proto_lambda * self.batch_size * pair)
         return loss_list
 
-    # ------------------------------------------------------------------ fused, autograd-free step
-    def _step_buffers(self):
-        st = self._storage
-        if self._buf is None or self._buf["key"] != (st.data_ptr(), st.device):
-            K = self.n_layers
-            new = lambda: torch.empty_like(st)  # noqa: E731
-            self._buf = dict(key=(st.data_ptr(), st.device), E=[None] + [new() for _ in range(K)], S=new(), final=new(),
-                             g_final=new(), G0=new(), GL=new(), chain=[new(), new()], grad=None,
-                             parts=torch.empty(4, dtype=torch.float32, device=st.device))
-        return self._buf
-
-    def fused_loss_and_grad(self, users, pos, neg, loss_out=None):
-        """The four losses (device tensor; the prototype entry 0 before the warm-up ends) and d(sum) / d(weights) in the two
-        parameters' .grad, as one fixed chain of library calls."""
-        if not self._is_packed():
-            self._pack()
-        st = self._storage
-        U, I, K, L = self.dataset.num_users, self.dataset.num_items, self.n_layers, 2 * self.cl_layer
-        users, pos, neg = (t.long().contiguous() for t in (users, pos, neg))
-        buf = self._step_buffers()
-        self._eval_cache = None
-        if loss_out is None:
-            loss_out = torch.empty(4, dtype=torch.float32, device=st.device)
-        E, G0, GL = buf["E"], buf["G0"], buf["GL"]
-        E[0] = st
-        # layers 1..K and their mean: the running sum rides in the product's epilogue
-        for k in range(1, K + 1):
-            last = k == K
-            ops.spmm_ex_raw(self.Graph, E[k - 1], Y=E[k], sum_in=E[0] if k == 1 else buf["S"],
-                            sum_out=buf["final"] if last else buf["S"], div=float(K + 1) if last else 1.0)
-        for t in (buf["g_final"], G0, GL):
-            t.zero_()
-        # BPR on the mean; the regulariser's gradient lands with layer 0's
-        ops.bpr_fused_raw(buf["final"], st, users, pos, neg, U, self.reg_lambda, buf["g_final"], G0, loss=loss_out[0:2])
-        parts = buf["parts"].zero_()
+    # ------------------------------------------------------------------ fused step: the hook of LayerChainRecommender
+    def _ssl_raw(self, E, G, users, pos, parts, loss_out):
+        """The prototype entry is 0 before the warm-up ends."""
+        U, I, L = self.dataset.num_users, self.dataset.num_items, 2 * self.cl_layer
+        G0, GL = G[0], G[L]
         ops.table_nce_raw(E[0], 0, U, [E[L]], [users], users, [self.ssl_lambda], self.temperature, loss=parts[0:1],
                           g_table=G0, g_queries=[GL])
         ops.table_nce_raw(E[0], U, I, [E[L]], [pos + U], pos, [self.ssl_lambda * self.alpha], self.temperature,
@@ -171,66 +128,6 @@ class NCL(PackedRecommender):
             loss_out[3] = (parts[2] + parts[3]) * scale
         else:
             loss_out[3] = 0.0
-        # g_k = A g_(k+1) + g_final / (K + 1) + g_ssl_k, from the last layer down (only layers 0 and L carry a contrastive term)
-        share = 1.0 / (K + 1)
-        cur = buf["chain"][K % 2]
-        if L == K:
-            ops.lincomb_raw(cur, GL, 1.0, buf["g_final"], share)
-        else:
-            ops.lincomb_raw(cur, buf["g_final"], share)
-        for k in range(K - 1, -1, -1):
-            if k == 0 or k == L:
-                add = G0 if k == 0 else GL
-                ops.lincomb_raw(add, add, 1.0, buf["g_final"], share)
-            else:
-                add = buf["S"]
-                ops.lincomb_raw(add, buf["g_final"], share)
-            nxt = buf["chain"][k % 2]
-            self.Graph.spmm_raw(cur, addend=add, out=nxt)
-            cur = nxt
-        buf["grad"] = cur
-        self.user_embedding.weight.grad = cur[:U]
-        self.item_embedding.weight.grad = cur[U:]
-        return loss_out
-
-    def fused_train_step(self, users, pos, neg, loss_out, optimizer):
-        """fused_loss_and_grad + the dense Adam step of the packed panel, in the state of `optimizer` (an ops.Adam over exactly
-        the two tables; its step / exp_avg / exp_avg_sq stay the single source of truth, the moments re-homed once into
-        packed [n, d] panels that the state entries view, as in PackedRecommender).  False — nothing done — otherwise."""
-        uw, iw = self.user_embedding.weight, self.item_embedding.weight
-        if not isinstance(optimizer, ops.Adam) or len(optimizer.param_groups) != 1:
-            return False
-        group = optimizer.param_groups[0]
-        if len(group["params"]) != 2 or group["params"][0] is not uw or group["params"][1] is not iw:
-            return False
-        if not self._is_packed():
-            self._pack()
-        U = self.dataset.num_users
-        st_u, st_i = optimizer.state[uw], optimizer.state[iw]
-        packed = getattr(self, "_packed_moments", None)
-        if (packed is None or packed[0].device != self._storage.device or not st_u or not st_i
-                or st_u["exp_avg"].data_ptr() != packed[0].data_ptr() or st_i["exp_avg_sq"].data_ptr() != packed[1][U:].data_ptr()):
-            m, v = torch.zeros_like(self._storage), torch.zeros_like(self._storage)
-            for st, sl in ((st_u, slice(0, U)), (st_i, slice(U, None))):
-                if st:  # the optimizer has already stepped the other way: keep what it accumulated
-                    m[sl].copy_(st["exp_avg"])
-                    v[sl].copy_(st["exp_avg_sq"])
-                st.setdefault("step", 0)
-                st["exp_avg"], st["exp_avg_sq"] = m[sl], v[sl]
-            packed = self._packed_moments = (m, v)
-        if st_u["step"] != st_i["step"]:
-            return False
-        self.fused_loss_and_grad(users, pos, neg, loss_out)
-        step = int(st_u["step"]) + 1
-        b1, b2 = group["betas"]
-        ops.adam_step_raw(self._storage, self._buf["grad"], packed[0], packed[1], group["lr"], step, b1, b2, group["eps"])
-        st_u["step"] = st_i["step"] = step
-        if not getattr(self, "keep_fused_grad", False):
-            uw.grad = iw.grad = None
-        return True
-
-    def prefetch_batch(self, users, pos, neg):
-        """Nothing to prepare ahead: the step's index work is inside its calls."""
 
 
 class Trainer():

@@ -11,7 +11,7 @@ import utility.utility_data.data_graph as data_graph
 import utility.utility_function.losses as losses
 import utility.utility_train.trainer as trainer
 from idgrec_amd import ops
-from idgrec_amd.modeling import PackedRecommender
+from idgrec_amd.modeling import PackedRecommender, adam_group_over
 from idgrec_amd.ngcf import NgcfEngine
 
 
@@ -73,11 +73,8 @@ class NGCF(PackedRecommender):
     def fused_train_step(self, users, pos, neg, loss_out, optimizer):
         """forward + backward + every Adam update as ONE chain of kernels; False (nothing done) unless `optimizer` is an
         idgrec_amd.ops.Adam over exactly this model's parameters.  Its state stays the single source of truth."""
-        params = list(self.parameters())
-        if not isinstance(optimizer, ops.Adam) or len(optimizer.param_groups) != 1:
-            return False
-        group = optimizer.param_groups[0]
-        if len(group["params"]) != len(params) or any(a is not b for a, b in zip(group["params"], params)):
+        group = adam_group_over(optimizer, list(self.parameters()))
+        if group is None:
             return False
         eng = self.ngcf_engine()
         uw, iw = self.user_embedding.weight, self.item_embedding.weight
