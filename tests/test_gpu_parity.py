@@ -259,7 +259,7 @@ def test_bpr_touched_bitmap_and_stored_rows(ops, golden_small):
 
 
 @pytest.mark.parametrize("world,B,d,U,I", [(1, 128, 64, 300, 200), (2, 16, 64, 40, 30), (5, 200, 64, 300, 200), (8, 1024, 64, 3000, 2000),
-                                           (3, 4000, 100, 5000, 3000), (4, 21, 7, 9, 5)])
+                                           (3, 4000, 100, 5000, 3000), (4, 21, 7, 9, 5), (3, 50, 20, 40, 30), (3, 50, 100, 40, 30)])
 @pytest.mark.parametrize("fold_clear", [False, True])
 def test_gradient_row_messages_merge_in_rank_order(ops, world, B, d, U, I, fold_clear):
     """idg_bpr_pack_rows_f32 / idg_bpr_unpack_rows_f32 (replicas exchange gradient rows before the backward propagation):
