@@ -124,6 +124,8 @@ PROTOTYPES = {
     "idg_kmeans_assign_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, c_vp, c_vp]),
     "idg_kmeans_update_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, c_vp, c_vp]),
     "idg_kmeans_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "idg_rows_normalize_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_float, c_vp, c_vp, c_vp]),
+    "idg_rows_normalize_bwd_f32": (C.c_int, [c_vp, c_vp, c_vp, C.c_float, c_vp, C.c_float, c_vp, c_vp, C.c_int64, C.c_int64, c_vp]),
     "idg_infonce_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "idg_infonce_cross_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float, c_vp, c_vp,
                                         C.c_float, c_vp, c_vp]),

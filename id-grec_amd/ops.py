@@ -767,6 +767,127 @@ def propagate_mean(graph, E0, K, include_layer0=True):
     return _PropagateMean.apply(E0, graph, int(K), bool(include_layer0))
 
 
+# ------------------------------------------------------------------- row normalisation (LightGCN++)
+ROWNORM_MAX_WIDTH = 512  # idg_rows_normalize*_f32: 1 <= d <= 512
+ROWNORM_EPS = 1e-12  # models/LightGCN_pp.py:83
+
+
+def _rownorm_args(who, X, norms=None, **panels):
+    """The checks of the row-normalisation calls; returns (n, d).  X: contiguous float32 [n, d]; the named panels (None
+    allowed) like it; norms: contiguous float32 [n]."""
+    if X.dim() != 2:
+        raise ValueError("%s: the panel must be [n, d] (got %s)" % (who, tuple(X.shape)))
+    n, d = (int(v) for v in X.shape)
+    if n < 1 or d < 1 or d > ROWNORM_MAX_WIDTH:
+        raise ValueError("%s: %d rows of width %d (at least one row, width 1 .. %d is built)" % (who, n, d, ROWNORM_MAX_WIDTH))
+    if X.dtype != torch.float32 or not X.is_contiguous():
+        raise TypeError("%s: the panel must be contiguous float32 (got %s, contiguous=%s)" % (who, X.dtype, X.is_contiguous()))
+    for name, t in panels.items():
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (n, d)):
+            raise TypeError("%s: %s must be a contiguous float32 [%d, %d] tensor" % (who, name, n, d))
+    if norms is not None and (norms.dtype != torch.float32 or not norms.is_contiguous() or tuple(norms.shape) != (n,)):
+        raise TypeError("%s: norms must be a contiguous float32 [%d] tensor" % (who, n))
+    _require_device(X, norms, *panels.values())
+    return n, d
+
+
+def rows_normalize_raw(X, Y=None, norms=None, eps=ROWNORM_EPS):
+    """idg_rows_normalize_f32: norms[r] = ||X[r]||_2, Y[r] = X[r] / (norms[r] + eps).  Y may be X (in place).
+    Returns (Y, norms)."""
+    n, d = _rownorm_args("rows_normalize_raw", X, norms, Y=Y)
+    Y = torch.empty_like(X) if Y is None else Y
+    norms = torch.empty(n, dtype=torch.float32, device=X.device) if norms is None else norms
+    check(lib.idg_rows_normalize_f32(_ptr(X), n, d, float(eps), _ptr(Y), _ptr(norms), _stream()), "idg_rows_normalize_f32")
+    return Y, norms
+
+
+def rows_normalize_bwd_raw(T, Y, norms, G=None, a=0.0, add2=None, out=None, eps=ROWNORM_EPS):
+    """idg_rows_normalize_bwd_f32: out[r] = a G[r] + add2[r] + J_r(T[r]), J the backward of the normalisation of row r from the
+    Y and norms rows_normalize_raw returned (J(t) = t / eps at a zero row).  G and add2 may each be None; out may be T, G
+    or add2.  Returns out."""
+    if norms is None or Y is None:
+        raise TypeError("rows_normalize_bwd_raw: Y and norms (what rows_normalize_raw returned) are needed")
+    n, d = _rownorm_args("rows_normalize_bwd_raw", T, norms, Y=Y, G=G, add2=add2, out=out)
+    out = torch.empty_like(T) if out is None else out
+    check(lib.idg_rows_normalize_bwd_f32(_ptr(T), _ptr(Y), _ptr(norms), float(eps), _ptr(G), float(a), _ptr(add2), _ptr(out),
+                                         n, d, _stream()), "idg_rows_normalize_bwd_f32")
+    return out
+
+
+class _RowsNormalize(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, eps):
+        Y, norms = rows_normalize_raw(_f32c(X, "X"), eps=eps)
+        ctx.save_for_backward(Y, norms)
+        ctx.eps = eps
+        return Y
+
+    @staticmethod
+    def backward(ctx, gY):
+        Y, norms = ctx.saved_tensors
+        return rows_normalize_bwd_raw(_f32c(gY, "grad"), Y, norms, eps=ctx.eps), None
+
+
+def rows_normalize(X, eps=ROWNORM_EPS):
+    """X / (torch.norm(X, dim=1) + eps)[:, None], differentiable (models/LightGCN_pp.py:83-84)."""
+    return _RowsNormalize.apply(X, float(eps))
+
+
+class _PropagateNormalized(torch.autograd.Function):
+    """The encoder of LightGCN++: X_k = A rownorm(X_(k-1)), final = gamma E0 + (1 - gamma) mean(X_1 .. X_K).  Saves the
+    normalised inputs N_0 .. N_(K-1) and their norms; the layer outputs themselves are never kept (X_k is normalised in
+    place, the running sum rides in the product's epilogue)."""
+
+    @staticmethod
+    def forward(ctx, E0, graph, K, gamma):
+        E0 = _f32c(E0, "E0")
+        _rownorm_args("propagate_normalized", E0)
+        if E0.shape[0] != graph.n_cols or graph.n_rows != graph.n_cols:
+            raise ValueError("propagate_normalized: E0 must be [%d, d] for this graph, got %s" % (graph.n_cols, tuple(E0.shape)))
+        S = torch.empty_like(E0)
+        Ns, norms = [], []
+        X = E0
+        for k in range(1, K + 1):
+            # N_(k-1): out of place for the parameters' own panel, in place for a layer output
+            N, nrm = rows_normalize_raw(X, Y=None if k == 1 else X)
+            Ns.append(N)
+            norms.append(nrm)
+            last = k == K
+            X = None if last else torch.empty_like(E0)
+            spmm_ex_raw(graph, N, Y=X, sum_in=None if k == 1 else S, sum_out=S, div=float(K) if last else 1.0)
+        final = torch.empty_like(E0)
+        lincomb_raw(final, E0, gamma, S, 1.0 - gamma)
+        ctx.save_for_backward(*Ns, *norms)
+        ctx.graph, ctx.K, ctx.gamma = graph, K, gamma
+        return final
+
+    @staticmethod
+    def backward(ctx, g):
+        K, gamma, At = ctx.K, ctx.gamma, ctx.graph.T
+        if At is None:
+            raise RuntimeError("propagate_normalized backward needs the transposed graph (Graph(..., symmetric=False) builds it)")
+        Ns, norms = ctx.saved_tensors[:K], ctx.saved_tensors[K:]
+        g = _f32c(g, "grad")
+        c = (1.0 - gamma) / K
+        H, T = torch.empty_like(g), torch.empty_like(g)
+        lincomb_raw(H, g, c)  # H_K = c g
+        for k in range(K, 0, -1):
+            At.spmm_raw(H, out=T)
+            # H_(k-1) = a g + J_(k-1)(T), written over T
+            rows_normalize_bwd_raw(T, Ns[k - 1], norms[k - 1], G=g, a=c if k > 1 else gamma, out=T)
+            H, T = T, H
+        return H, None, None, None
+
+
+def propagate_normalized(graph, E0, K, gamma):
+    """gamma E0 + (1 - gamma) mean_k(X_k), X_k = A rownorm(X_(k-1)), k = 1..K — LightGCN_pp.aggregate
+    (models/LightGCN_pp.py:75-96).  `graph` need not be symmetric: the backward runs on graph.T."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("propagate_normalized: K = %d layers (at least 1)" % K)
+    return _PropagateNormalized.apply(E0, graph, K, float(gamma))
+
+
 # ------------------------------------------------------------------------------------ BPR
 _bpr_ws_cache = {}
 

@@ -742,6 +742,29 @@ int idg_kmeans_f32(const float* X, int64_t ldx, int64_t N, int64_t d, int64_t K,
                    float* inertia, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * DEVICE: row normalisation of a panel and its backward, the per-layer step of LightGCN++ (Lee et al. RecSys'24;
+ * models/LightGCN_pp.py:82-84 of the reference: x / (torch.norm(x, dim=1) + 1e-12)[:, None]).
+ *
+ * Panels are contiguous fp32 [n, d], 16-byte aligned, 1 <= d <= 512, n < 2^31; norms is [n]; eps > 0.
+ * idg_rows_normalize_f32: norms[r] = ||X[r]||_2, Y[r] = X[r] / (norms[r] + eps).  A zero row gives norms[r] = 0 and Y[r] = 0
+ *   exactly.
+ * idg_rows_normalize_bwd_f32: out[r] = a G[r] + add2[r] + J_r(T[r]); G and add2 may each be NULL (a is then not read).  J is
+ *   the backward of the row's normalisation, from the Y and norms the forward call saved: with n = norms[r], e = eps,
+ *   y = Y[r]:  J(t) = (t - y <y, t> (n + e) / n) / (n + e) for n > 0, and J(t) = t / e for n == 0 (torch's norm has gradient 0
+ *   at the origin; exact: the saved y is 0 there).
+ * One row is held by one group of 4 .. 64 lanes in registers between a shuffle reduction and the store (float4 accesses where
+ * d % 4 == 0, a scalar path for every other width): every input panel is read once, every output written once; no LDS, no
+ * atomics, the same bits every run.
+ * Aliasing.  Forward: Y may be X (in place); any other overlap of Y with X, and any overlap of norms with X or Y, is
+ * refused.  Backward: out may be T, G or add2 (the same pointer); any other overlap of out with one of them, and any
+ * overlap of out with Y or norms, is refused.  The inputs may alias one another freely.
+ * Arguments are checked on the host before any device work (IDG_E_INVALID, idg_last_error).
+ * ---------------------------------------------------------------------------------- */
+int idg_rows_normalize_f32(const float* X, int64_t n, int64_t d, float eps, float* Y, float* norms, void* stream);
+int idg_rows_normalize_bwd_f32(const float* T, const float* Y, const float* norms, float eps, const float* G, float a,
+                               const float* add2, float* out, int64_t n, int64_t d, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * DEVICE: dense Adam step  (torch.optim.Adam defaults, utility/utility_train/trainer.py:11,56:
  * betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad).  step is 1-based.  The
  * hyper-parameters are doubles because torch forms lr/(1-beta1^t) and sqrt(1-beta2^t) in

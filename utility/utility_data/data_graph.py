@@ -45,6 +45,31 @@ def sparse_adjacency_matrix_with_self(data):
     return _cached(data, "pre_A_with_self", lambda: _bipartite(data, True))
 
 
+def sparse_adjacency_matrix_asymmetric(data, alpha, beta):
+    """D^-alpha [[0,R],[R^T,0]] D^-beta, float32 (cache: pre_A_{alpha}_{beta}.npz, the floats as Python prints them) — the
+    adjacency of LightGCN++ (models/LightGCN_pp.py:42-73).  alpha != beta makes it differ from its transpose.  The
+    reference's expressions on CSR operands: float32 degrees raised to -alpha and -beta in float32, infinities (a node
+    without an edge under a positive exponent) replaced by 0, and every value the float32 product (d_i^-alpha . a_ij) .
+    d_j^-beta, left factor first."""
+    alpha, beta = float(alpha), float(beta)
+
+    def build():
+        R = data.user_item_net.astype(np.float32).tocsr()
+        A = sp.bmat([[None, R], [R.T, None]], format="csr", dtype=np.float32)
+        A.sort_indices()
+        deg = np.array(A.sum(axis=1))  # float32 [n, 1], as the reference's row sums
+        with np.errstate(divide="ignore"):
+            left = (deg ** -alpha).flatten()
+            right = (deg ** -beta).flatten()
+        left[np.isinf(left)] = 0.0
+        right[np.isinf(right)] = 0.0
+        mat = sp.diags(left).dot(A).dot(sp.diags(right)).tocsr()
+        mat.sort_indices()
+        return mat
+
+    return _cached(data, "pre_A_%s_%s" % (alpha, beta), build)
+
+
 def sparse_adjacency_matrix_R(data):
     """Rectangular D_u^-1/2 R D_i^-1/2 (cache: pre_R.npz) — used only by models outside the
     LightGCN hot path (EGCF / CVGA / LightGCL); kept on SciPy with the reference's expression."""
