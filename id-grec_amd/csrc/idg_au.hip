@@ -20,10 +20,14 @@
 #include <cmath>
 
 #include "idg_common.h"
+#include "idg_device.h"
 
 namespace {
 
-constexpr int WAVE = 64;
+using idg::align256;
+using idg::f32x16;
+using idg::WAVE;
+using idg::wave_sum;
 constexpr int BLOCK = 256;
 constexpr int TS = 64;        // pair tile: 64 stripe rows x 64 columns
 constexpr int LLD = TS + 4;   // LDS row stride (floats) of the MFMA form
@@ -31,14 +35,6 @@ constexpr int GK = 16;        // feature chunk of the generic form's Gram tile
 constexpr int MAX_NF = 4;     // MFMA form: d = 64 NF, NF <= 4 (d <= 256)
 constexpr int TARGET_WG = 256;
 constexpr float NORM_EPS = 1e-12f;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-  return v;
-}
-
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 // slices of a stripe's column tiles: enough workgroups (2 sets x stripes x slices) to cover the chip, a function of B only
 struct Slices {
@@ -152,8 +148,6 @@ __device__ __forceinline__ float pair_s(const float* __restrict__ qs, int64_t B,
 //   grid: (slices, stripes, 2 sets).  Per column tile: the 64 x 64 Gram tile (each wave a 32 x 32 quarter; operands from
 //   64-deep LDS chunks of the stripe's and the tile's rows), s into LDS, the row sums, then S . X_tile (each wave 32 rows
 //   x NF 32-wide feature tiles, the S operand from LDS, X's rows straight from memory: 128-byte runs per lane half).
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 template <int NF>
 __global__ __launch_bounds__(BLOCK) void au_pair_mfma_kernel(const float* __restrict__ X, const float* __restrict__ q,
                                                              int64_t B, int per, int gs, float* __restrict__ pr,
@@ -206,7 +200,7 @@ __global__ __launch_bounds__(BLOCK) void au_pair_mfma_kernel(const float* __rest
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = tr + (r & 3) + 8 * (r >> 2) + 4 * h, col = tc + i;
+      const int row = tr + idg::mfma_c_row(r, h), col = tc + i;
       s_s[row * LLD + col] = pair_s(qs, B, i0 + row, j0 + col, g[r]);
     }
     __syncthreads();
@@ -232,7 +226,7 @@ __global__ __launch_bounds__(BLOCK) void au_pair_mfma_kernel(const float* __rest
     const int64_t fc = 32 * ((wave & 1) + 2 * nf) + i;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int64_t row = i0 + tr + (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int64_t row = i0 + tr + idg::mfma_c_row(r, h);
       if (row < B) pacc[(base * B + row) * d + fc] = acc[nf][r];
     }
   }

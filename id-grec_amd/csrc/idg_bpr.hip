@@ -13,10 +13,13 @@
 #include <cstdlib>
 
 #include "idg_common.h"
+#include "idg_device.h"
 
 namespace {
 
-constexpr int WAVE = 64;
+using idg::align256;
+using idg::WAVE;
+using idg::wave_sum;
 constexpr int BLOCK = 256;
 constexpr int LDS_SORT_MAX = 8192;  // (key,slot) pairs one workgroup sorts in LDS
 // IDG_SORT_SINGLE_BLOCK=1: lists of 1025..8192 pairs sorted by ONE workgroup as before round 5 (A/B runs; same result)
@@ -24,12 +27,6 @@ static const bool g_single_block_sort = [] {
   const char* e = std::getenv("IDG_SORT_SINGLE_BLOCK");
   return e && e[0] == '1';
 }();
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-  return v;
-}
 
 struct BprArgs {
   const float* fin;
@@ -765,8 +762,6 @@ __global__ __launch_bounds__(BLOCK) void bpr_unpack_rows_kernel(const float* __r
     }
   }
 }
-
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 struct BprWs {
   size_t coef, loss_i, sq, keys, slots, skeys, sslots, temp, total;

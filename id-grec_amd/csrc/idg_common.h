@@ -1,4 +1,5 @@
-// Shared internals of libidgrec.so: error reporting and HIP call checking.
+// Shared internals of libidgrec.so: error reporting, HIP call checking and the host-side size arithmetic.
+// (Device-side helpers: idg_device.h, for .hip files only.)
 #pragma once
 #include <cstdarg>
 #include <cstddef>
@@ -23,6 +24,10 @@ inline int fail(int code, const char* fmt, ...) {
   set_error("%s", buf);
   return code;
 }
+
+// Workspace sub-buffers start at multiples of 256 bytes; padded operands are rounded up to whole tiles.
+inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // A row bitmap is about to be rewritten by a library call: live-unit lists registered for it (idg_graph_live_units)
 // describe its old contents and are dropped (idg_graph.hip).  bytes: extent of the write when the caller knows it (lists

@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "idg_common.h"
+#include "idg_device.h"
 #include "idg_dropout.h"
 
 namespace {
@@ -249,11 +250,6 @@ namespace {
 
 using idg::keep_scale;
 using idg::keep_scale4;
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(BLOCK) void ngcf_tail_fwd_kernel(const float* __restrict__ S1, const float* __restrict__ S2,
                                                               const float* __restrict__ b1, const float* __restrict__ b2,
@@ -271,7 +267,7 @@ __global__ __launch_bounds__(BLOCK) void ngcf_tail_fwd_kernel(const float* __res
     E[r * d + f] = e;
     ss += e * e;
   }
-  ss = wsum(ss);
+  ss = idg::wave_sum(ss);
   const float den = fmaxf(sqrtf(ss), 1e-12f);
   for (int64_t f = lane; f < d; f += 64) N[r * ldn + f] = E[r * d + f] / den;
 }
@@ -297,8 +293,8 @@ __global__ __launch_bounds__(BLOCK) void ngcf_tail_bwd_kernel(const float* __res
     ss += e * e;
     if (gN) dot += gN[r * ldgn + f] * e;
   }
-  ss = wsum(ss);
-  dot = wsum(dot);
+  ss = idg::wave_sum(ss);
+  dot = idg::wave_sum(dot);
   const float nrm = sqrtf(ss);
   const float den = fmaxf(nrm, 1e-12f);
   for (int64_t f = lane; f < d; f += 64) {
@@ -319,13 +315,6 @@ __global__ __launch_bounds__(BLOCK) void ngcf_tail_bwd_kernel(const float* __res
 // per wave — the one-wave-per-row form above moves 256 B per memory instruction at d = 64 and ran at a third of the
 // streaming rate (round 4).  Same per-element arithmetic; the row's sum of squares is formed 4 elements per lane, then
 // across the row's lanes.
-template <int LPR>
-__device__ __forceinline__ float row_sum(float v) {
-#pragma unroll
-  for (int m = LPR / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, LPR);
-  return v;
-}
-
 template <int LPR>
 __global__ __launch_bounds__(BLOCK) void ngcf_tail_fwd_vec_kernel(const float* __restrict__ S1, const float* __restrict__ S2,
                                                                   const float* __restrict__ b1, const float* __restrict__ b2,
@@ -350,7 +339,7 @@ __global__ __launch_bounds__(BLOCK) void ngcf_tail_fwd_vec_kernel(const float* _
     e[c] = a * kp[c];
     ss += e[c] * e[c];
   }
-  ss = row_sum<LPR>(ss);
+  ss = idg::lanes_sum<LPR>(ss);
   const float den = fmaxf(sqrtf(ss), 1e-12f);
   *reinterpret_cast<float4*>(E + r * d + f) = make_float4(e[0], e[1], e[2], e[3]);
   *reinterpret_cast<float4*>(N + r * ldn + f) = make_float4(e[0] / den, e[1] / den, e[2] / den, e[3] / den);
@@ -385,8 +374,8 @@ __global__ __launch_bounds__(BLOCK) void ngcf_tail_bwd_vec_kernel(const float* _
   float ss = 0.f, dot = 0.f;
 #pragma unroll
   for (int c = 0; c < 4; ++c) ss += ev[c] * ev[c], dot += gn[c] * ev[c];
-  ss = row_sum<LPR>(ss);
-  dot = row_sum<LPR>(dot);
+  ss = idg::lanes_sum<LPR>(ss);
+  dot = idg::lanes_sum<LPR>(dot);
   const float nrm = sqrtf(ss);
   const float den = fmaxf(nrm, 1e-12f);
   float out[4], kp[4];
@@ -578,7 +567,7 @@ int idg_rows_add2_f32(float* dst, int64_t ldd, const float* a, int64_t lda, cons
 // accumulator, both products of the backward share one A operand.  Exact fp32 products and accumulation.
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using idg::f32x16;
 
 // Persistent waves: wave w of the launch owns output column tile w % nct (forward) / input feature tile w % nkt
 // (backward) and keeps that tile's weights — 32 of W1 and 32 of W2 per lane — in registers while it walks the row tiles
@@ -627,7 +616,7 @@ __global__ __launch_bounds__(BLOCK) void ngcf_transform_fwd_kernel(const float* 
       // C/D map: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t rr = r0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int64_t rr = r0 + idg::mfma_c_row(r, h);
         if (rr < n) {
           float* o = S + rr * d2 + c0 + i;
           *o = kc == 0 ? acc[r] : *o + acc[r];  // further 64-deep chunks of a wide layer add to the first one's sums
@@ -702,7 +691,7 @@ __global__ __launch_bounds__(BLOCK) void ngcf_transform_bwd_kernel(const float* 
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int64_t rr = r0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int64_t rr = r0 + idg::mfma_c_row(r, h);
       if (rr < n) {
         const int64_t o = rr * d1 + k1 + i;
         const float e = ego[o], sd = side[o];

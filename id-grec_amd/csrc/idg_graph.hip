@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "idg_common.h"
+#include "idg_device.h"
 
 #ifndef IDG_ROWS_UNROLL
 #define IDG_ROWS_UNROLL 8  // panel rows in flight per lane group in the row-restricted / sparse-input kernels (few lane groups
@@ -302,6 +303,7 @@ __device__ __forceinline__ float noise_row_scale(const Epilogue& ep, int64_t r, 
     const float4 u = noise4(ep, r, b * LPR + l);
     ss += u.x * u.x + u.y * u.y + u.z * u.z + u.w * u.w;
   }
+  // idg::lanes_sum<LPR> written out: through the helper the SpMM kernels with this epilogue compile to other code
 #pragma unroll
   for (int o = LPR / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, LPR);
   return ep.noise_eps / fmaxf(sqrtf(ss), 1e-12f);
@@ -1349,7 +1351,7 @@ __device__ __forceinline__ float generic_noise_scale(const Epilogue& ep, int64_t
     for (int c = 0; c < 4; ++c)
       if (fb * 4 + c < d) ss += uu[c] * uu[c];
   }
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  ss = idg::wave_sum(ss);
   return ep.noise_eps / fmaxf(sqrtf(ss), 1e-12f);
 }
 
@@ -2666,7 +2668,7 @@ int idg_perturb_f32(const float* X, float* Y, int64_t n, int64_t d, const uint32
 size_t idg_propagate_workspace_bytes(const idg_graph* g, int64_t d) {
   if (!g || d <= 0) return 0;
   // two ping-pong panels + the split-row partials
-  const size_t panel = ((size_t)std::max(g->n_rows, g->n_cols) * (size_t)d * sizeof(float) + 255) / 256 * 256;
+  const size_t panel = idg::align256((size_t)std::max(g->n_rows, g->n_cols) * (size_t)d * sizeof(float));
   return 2 * panel + idg_spmm_workspace_bytes(g, d);
 }
 
@@ -2680,7 +2682,7 @@ static int propagate_common(const idg_graph* g, const float* in, float* out, int
   IDG_REQUIRE(K >= 1, "idg_propagate: K must be >= 1 (got %d)", K);
   IDG_REQUIRE(d > 0, "idg_propagate: d must be > 0");
   IDG_REQUIRE(in != out, "idg_propagate: in-place propagation is not supported");
-  const size_t panel = ((size_t)g->n_rows * (size_t)d * sizeof(float) + 255) / 256 * 256;
+  const size_t panel = idg::align256((size_t)g->n_rows * (size_t)d * sizeof(float));
   float* P[2] = {reinterpret_cast<float*>(ws), reinterpret_cast<float*>((char*)ws + panel)};
   void* partials = (char*)ws + 2 * panel;
   const float cnt = (float)(K + (include0 ? 1 : 0));
@@ -2760,8 +2762,8 @@ static int propagate_common(const idg_graph* g, const float* in, float* out, int
 // ---- clean pass + perturbed views with a shared first product and ONE multi-panel launch for the last layer ----
 size_t idg_propagate_views_workspace_bytes(const idg_graph* g, int64_t d, int n_views) {
   if (!g || d <= 0 || n_views < 0 || n_views + 1 > MAX_PANELS) return 0;
-  const size_t panel = ((size_t)std::max(g->n_rows, g->n_cols) * (size_t)d * sizeof(float) + 255) / 256 * 256;
-  const size_t part = (idg_spmm_workspace_bytes(g, d) + 255) / 256 * 256;
+  const size_t panel = idg::align256((size_t)std::max(g->n_rows, g->n_cols) * (size_t)d * sizeof(float));
+  const size_t part = idg::align256(idg_spmm_workspace_bytes(g, d));
   return (size_t)(n_views + 1) * (2 * panel + part);
 }
 
@@ -2777,8 +2779,8 @@ int idg_propagate_views_f32(const idg_graph* g, const float* E0, int K, int64_t 
   hipStream_t st = (hipStream_t)stream;
   const int np = n_views + 1;
   const int64_t n = g->n_rows;
-  const size_t panel = ((size_t)n * (size_t)d * sizeof(float) + 255) / 256 * 256;
-  const size_t part = (idg_spmm_workspace_bytes(g, d) + 255) / 256 * 256;
+  const size_t panel = idg::align256((size_t)n * (size_t)d * sizeof(float));
+  const size_t part = idg::align256(idg_spmm_workspace_bytes(g, d));
   char* base = reinterpret_cast<char*>(ws);
   float* P[MAX_PANELS][2];
   float* partials[MAX_PANELS];

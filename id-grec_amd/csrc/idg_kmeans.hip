@@ -26,31 +26,22 @@
 #include <cmath>
 
 #include "idg_common.h"
+#include "idg_tile128.h"
 
 namespace {
 
-constexpr int WAVE = 64;
-constexpr int BLOCK = 256;
-constexpr int T = 128;        // rows of an X tile / centroids of a C tile
-constexpr int KC = 32;        // feature chunk of a score tile
-constexpr int LK = KC + 4;    // its LDS row stride (floats)
+using namespace idg::tile128;  // T = 128 rows of an X tile / centroids of a C tile, LG the row stride of the distance tile
+using idg::align256;
+using idg::f32x16;
+using idg::mfma_c_row;
+using idg::round_up;
+using idg::WAVE;
+using idg::wave_sum;
+
 constexpr int MAX_NDT = 8;    // d <= 256
 constexpr int MAX_CHUNKS = 64;
 constexpr int TARGET_WGS = 512;  // two 66 KB workgroups per CU
-constexpr int LG = T + 1;     // row stride of the distance tile
-constexpr int LDS_FLOATS = T * LG;  // the distance tile; the score operands (2 x 128 x LK) alias it
 constexpr int RED = 1024;     // threads of the one-workgroup scan / reduction kernels
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-  return v;
-}
-
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 struct Geo {
   int64_t dp, Np, Kp;
@@ -140,39 +131,7 @@ __global__ __launch_bounds__(BLOCK, 2) void km_tile_kernel(const float* __restri
     const int64_t y0 = (int64_t)p * T;
     const float* Y = Cp + y0 * dp;
     f32x16 s[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[m][n][r] = 0.f;
-    // ---- S = X C^T
-    for (int kc = 0; kc < NDT; ++kc) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int e = tid + BLOCK * j, rr = e >> 3, c4 = (e & 7) * 4;
-        *reinterpret_cast<float4*>(s_x + rr * LK + c4) = *reinterpret_cast<const float4*>(X + rr * dp + kc * KC + c4);
-        *reinterpret_cast<float4*>(s_y + rr * LK + c4) = *reinterpret_cast<const float4*>(Y + rr * dp + kc * KC + c4);
-      }
-      __syncthreads();
-      const float* pa = s_x + (64 * wr + i) * LK + 16 * h;
-      const float* pb = s_y + (64 * wc + i) * LK + 16 * h;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float4 a0 = *reinterpret_cast<const float4*>(pa + 4 * c);
-        const float4 a1 = *reinterpret_cast<const float4*>(pa + 32 * LK + 4 * c);
-        const float4 b0 = *reinterpret_cast<const float4*>(pb + 4 * c);
-        const float4 b1 = *reinterpret_cast<const float4*>(pb + 32 * LK + 4 * c);
-#define IDG_KM_STEP(F)                                                                \
-  s[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.F, b0.F, s[0][0], 0, 0, 0);       \
-  s[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.F, b1.F, s[0][1], 0, 0, 0);       \
-  s[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.F, b0.F, s[1][0], 0, 0, 0);       \
-  s[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.F, b1.F, s[1][1], 0, 0, 0);
-        IDG_KM_STEP(x) IDG_KM_STEP(y) IDG_KM_STEP(z) IDG_KM_STEP(w)
-#undef IDG_KM_STEP
-      }
-      __syncthreads();
-    }
+    score_tile_128<NDT>(X, Y, s_x, s_y, s);  // ---- S = X C^T
     // ---- ||c||^2 - 2 <x, c> into the tile (2 s is exact: one rounding)
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
@@ -182,7 +141,7 @@ __global__ __launch_bounds__(BLOCK, 2) void km_tile_kernel(const float* __restri
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int rw = 64 * wr + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int rw = 64 * wr + 32 * m + mfma_c_row(r, h);
           s_g[rw * LG + col] = c2 - 2.f * s[m][n][r];
         }
     }
@@ -343,13 +302,8 @@ __global__ __launch_bounds__(RED) void km_sum_kernel(const float* __restrict__ v
   const int64_t per = (N + RED - 1) / RED, lo = tid * per < N ? tid * per : N, hi = lo + per < N ? lo + per : N;
   double acc = 0.;
   for (int64_t r = lo; r < hi; ++r) acc += (double)v[r];
-  s[tid] = acc;
-  __syncthreads();
-  for (int o = RED / 2; o > 0; o >>= 1) {
-    if (tid < o) s[tid] += s[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) out[0] = (float)s[0];
+  const double sum = idg::block_tree_sum<RED>(acc, s);
+  if (tid == 0) out[0] = (float)sum;
 }
 
 void launch_tile(int ndt, dim3 grid, hipStream_t st, const float* Xp, const float* Cp, const float* cn, int per, int nkt,

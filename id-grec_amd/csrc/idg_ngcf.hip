@@ -18,11 +18,12 @@
 #include <cstdint>
 
 #include "idg_common.h"
+#include "idg_device.h"
 #include "idg_dropout.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using idg::f32x16;
 
 constexpr int BLOCK = 256;
 constexpr int D = 64;
@@ -30,16 +31,6 @@ constexpr int RB = 64;   // rows per workgroup tile
 constexpr int LDT = 68;  // LDS row stride in floats: rows 16-byte aligned, b128 operand reads of 16 rows hit 64 distinct banks
 constexpr int BWD_WGS = 512;  // resident workgroups of the backward kernel (2 x 512 threads per CU) = most slices of its parameter-gradient sums
 constexpr int RG = 16;
-
-template <int LPR>
-__device__ __forceinline__ float row_sum(float v) {
-#pragma unroll
-  for (int m = LPR / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, LPR);
-  return v;
-}
-
-// C/D map of v_mfma_f32_32x32x2_f32: register r of lane (i, h) holds row (r & 3) + 8 (r >> 2) + 4 h, column i
-__device__ __forceinline__ int c_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 __global__ __launch_bounds__(BLOCK, 4) void ngcf_layer_fwd64_kernel(const float* __restrict__ side, const float* __restrict__ ego,
                                                                  const float* __restrict__ W1, const float* __restrict__ W2,
@@ -87,7 +78,7 @@ __global__ __launch_bounds__(BLOCK, 4) void ngcf_layer_fwd64_kernel(const float*
     const float bb1 = b1[col], bb2 = b2[col];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int rr = 32 * rt + c_row(r, h);
+      const int rr = 32 * rt + idg::mfma_c_row(r, h);
       const float t = (acc[r] + bb1) + (0.f + bb2);  // idg_ngcf_tail_ex_f32 with S2 = NULL
       s_side[rr * LDT + col] = t > 0.f ? t : t * slope;
     }
@@ -102,7 +93,7 @@ __global__ __launch_bounds__(BLOCK, 4) void ngcf_layer_fwd64_kernel(const float*
     v.x *= kp[0], v.y *= kp[1], v.z *= kp[2], v.w *= kp[3];
     float ss = 0.f;
     ss += v.x * v.x, ss += v.y * v.y, ss += v.z * v.z, ss += v.w * v.w;
-    ss = row_sum<16>(ss);
+    ss = idg::lanes_sum<16>(ss);
     const float den = fmaxf(sqrtf(ss), 1e-12f);
     if (r0 + rr < n) {
       *reinterpret_cast<float4*>(E + (r0 + rr) * D + c4) = v;
@@ -191,8 +182,8 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void ngcf_layer_bwd64_kernel(
         float ss = 0.f, dot = 0.f;
 #pragma unroll
         for (int c = 0; c < 4; ++c) ss += ev[c] * ev[c], dot += gn[c] * ev[c];
-        ss = row_sum<16>(ss);
-        dot = row_sum<16>(dot);
+        ss = idg::lanes_sum<16>(ss);
+        dot = idg::lanes_sum<16>(dot);
         const float nrm = sqrtf(ss);
         const float den = fmaxf(nrm, 1e-12f);
         float kp[4];
@@ -228,7 +219,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void ngcf_layer_bwd64_kernel(
       float* ge_b = gEgo + r0 * D;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int rr = 32 * rt + c_row(r, h_l);
+        const int rr = 32 * rt + idg::mfma_c_row(r, h_l);
         if (rr <= last) {
           const float e = s_ego[rr * LDT + k1 + i_l], sd = s_side[rr * LDT + k1 + i_l];
           const int o = rr * D + k1 + i_l;
@@ -256,7 +247,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void ngcf_layer_bwd64_kernel(
   float* out = part + (int64_t)blockIdx.x * (2 * ww + 2 * D);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int m = 32 * mt + c_row(r, h), col = 32 * nt + i;
+    const int m = 32 * mt + idg::mfma_c_row(r, h), col = 32 * nt + i;
     out[m * D + col] = R[0][r];
     out[ww + D + m * D + col] = R[1][r];
   }

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "idg_common.h"
+#include "idg_device.h"
 
 namespace {
 
@@ -60,13 +61,6 @@ __device__ __forceinline__ void store_row(float* row, int d, int l, bool live, c
   }
 }
 
-template <int LPR>
-__device__ __forceinline__ float group_sum(float s) {
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, LPR);
-  return s;
-}
-
 template <int LPR, int NV, bool VEC>
 __global__ __launch_bounds__(BLOCK) void rows_normalize_kernel(const float* X, int64_t n, int d, float eps, float* Y,
                                                                float* __restrict__ norms) {
@@ -80,7 +74,7 @@ __global__ __launch_bounds__(BLOCK) void rows_normalize_kernel(const float* X, i
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < E; ++i) ss += x.v[i] * x.v[i];
-  ss = group_sum<LPR>(ss);
+  ss = idg::lanes_sum<LPR>(ss);
   const float nrm = sqrtf(ss), den = nrm + eps;
 #pragma unroll
   for (int i = 0; i < E; ++i) x.v[i] = x.v[i] / den;  // a zero row: 0 / eps == 0 exactly
@@ -105,7 +99,7 @@ __global__ __launch_bounds__(BLOCK) void rows_normalize_bwd_kernel(const float* 
   float dot = 0.f;
 #pragma unroll
   for (int i = 0; i < E; ++i) dot += y.v[i] * t.v[i];
-  dot = group_sum<LPR>(dot);
+  dot = idg::lanes_sum<LPR>(dot);
   const float nrm = live ? norms[r] : 1.f;
   const float den = nrm + eps;
   const float coef = nrm > 0.f ? dot * (den / nrm) : 0.f;

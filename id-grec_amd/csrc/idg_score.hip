@@ -20,14 +20,16 @@
 #include <cstdlib>
 
 #include "idg_common.h"
+#include "idg_device.h"
 
 namespace {
 
-constexpr int WAVE = 64;
+using idg::align256;
+using idg::f32x16;
+using idg::WAVE;
 constexpr int BLOCK = 256;
 constexpr int ITEMS_PER_WAVE = 256;  // 8 MFMA tiles per wave per launch row
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(BLOCK) void score_dense_kernel(const float* __restr
     if (j0 + i < I) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t b = b0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int64_t b = b0 + idg::mfma_c_row(r, h);
         if (b < Bt) {
           float s = acc[r];
           if (SIGMOID) s = sigmoidf_(s);
@@ -318,7 +320,7 @@ __global__ __launch_bounds__(BLOCK, 3) void score_topk_fused_kernel(const float*
       __syncthreads();  // every wave is done selecting from the previous slab
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int row = idg::mfma_c_row(r, h);
         s_score[row * FT_LD + 32 * wave + i] = acc0[r];
         s_score[(32 + row) * FT_LD + 32 * wave + i] = acc1[r];
       }
@@ -723,7 +725,7 @@ __global__ __launch_bounds__(SP_BLOCK, 4) void score_topk_spec_kernel(const floa
         float* s_score = s_buf[t & 1];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int row = idg::mfma_c_row(r, h);
           s_score[row * FT_LD + 32 * wave + i] = acc0[r];
           s_score[(32 + row) * FT_LD + 32 * wave + i] = acc1[r];
         }
@@ -777,7 +779,7 @@ __global__ __launch_bounds__(SP_BLOCK, 4) void score_topk_spec_kernel(const floa
       float* s_score = s_buf[t & 1];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int row = idg::mfma_c_row(r, h);
         s_score[row * FT_LD + 32 * wave + i] = acc0[r];
         s_score[(32 + row) * FT_LD + 32 * wave + i] = acc1[r];
       }
@@ -1013,16 +1015,15 @@ struct BoundWs {
   size_t vs, us, vbound, ubound, scalars, redo, total;
 };
 static inline BoundWs bound_layout(int64_t Bt, int64_t I, int64_t d, size_t base) {
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
   const size_t ks = (size_t)d / 16;
   BoundWs w{};
-  size_t o = up(base);
-  w.vs = o, o = up(o + (size_t)((I + 31) / 32) * (ks + 1) * 1024);  // (tiles of 32 items, KS + 1 blocks of 1 KiB)
-  w.us = o, o = up(o + (size_t)Bt * (ks + 2) * 32);
-  w.vbound = o, o = up(o + (size_t)I * 4);
-  w.ubound = o, o = up(o + (size_t)Bt * 4);
-  w.scalars = o, o = up(o + COLLECT_SCALARS * 4);  // the call's scalars (SC_*: idg_score_bf16.inc)
-  w.redo = o, o = up(o + (size_t)Bt * 4);  // batch indices of the users handed to topk_redo_kernel
+  size_t o = align256(base);
+  w.vs = o, o = align256(o + (size_t)((I + 31) / 32) * (ks + 1) * 1024);  // (tiles of 32 items, KS + 1 blocks of 1 KiB)
+  w.us = o, o = align256(o + (size_t)Bt * (ks + 2) * 32);
+  w.vbound = o, o = align256(o + (size_t)I * 4);
+  w.ubound = o, o = align256(o + (size_t)Bt * 4);
+  w.scalars = o, o = align256(o + COLLECT_SCALARS * 4);  // the call's scalars (SC_*: idg_score_bf16.inc)
+  w.redo = o, o = align256(o + (size_t)Bt * 4);  // batch indices of the users handed to topk_redo_kernel
   w.total = o;
   return w;
 }
@@ -1031,13 +1032,12 @@ struct CollectWs {
   size_t group_max, floor0, count, cand, tail;
 };
 static inline CollectWs collect_layout(int64_t Bt, int nc, int64_t I) {
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
   CollectWs w{};
   size_t o = 0;
-  w.group_max = o, o = up(o + (size_t)Bt * COLLECT_GROUPS_MAX * 4);
-  w.floor0 = o, o = up(o + (size_t)Bt * 4);
-  w.count = o, o = up(o + (size_t)Bt * (size_t)nc * 4);
-  w.cand = o, o = up(o + (size_t)Bt * (size_t)nc * (size_t)collect_cap_chunk(nc, I) * 8);
+  w.group_max = o, o = align256(o + (size_t)Bt * COLLECT_GROUPS_MAX * 4);
+  w.floor0 = o, o = align256(o + (size_t)Bt * 4);
+  w.count = o, o = align256(o + (size_t)Bt * (size_t)nc * 4);
+  w.cand = o, o = align256(o + (size_t)Bt * (size_t)nc * (size_t)collect_cap_chunk(nc, I) * 8);
   w.tail = o;
   return w;
 }

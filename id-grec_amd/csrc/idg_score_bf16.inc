@@ -277,7 +277,7 @@ __device__ __forceinline__ void bound_produce(const __bf16* __restrict__ Us, con
       A0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0_, bk, k == 0 ? zero16 : A0, 0, 0, 0);                          \
       A1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1_, bk, k == 0 ? zero16 : A1, 0, 0, 0);                          \
       _Pragma("unroll") for (int r = (16 * k) / KS1; r < (16 * (k + 1)) / KS1; ++r) {                                \
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;                                                              \
+        const int row = idg::mfma_c_row(r, h);                                                              \
         s_prev[row * FT_LD + 32 * wave + i] = P0[r];                                                                 \
         s_prev[(32 + row) * FT_LD + 32 * wave + i] = P1[r];                                                          \
       }                                                                                                              \
@@ -322,7 +322,7 @@ __device__ __forceinline__ void bound_produce(const __bf16* __restrict__ Us, con
     float* s_last = s_buf[(n_slabs - 1) & 1];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int row = idg::mfma_c_row(r, h);
       s_last[row * FT_LD + 32 * wave + i] = xb0[r];
       s_last[(32 + row) * FT_LD + 32 * wave + i] = xb1[r];
     }
@@ -405,7 +405,7 @@ __device__ __forceinline__ void bound_produce_lean(const __bf16* __restrict__ Us
     float* s_score = s_buf[t & 1];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int row = idg::mfma_c_row(r, h);
       s_score[row * FT_LD + 32 * wave + i] = a0[r];
       s_score[(32 + row) * FT_LD + 32 * wave + i] = a1[r];
     }

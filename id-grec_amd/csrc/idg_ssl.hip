@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "idg_common.h"
+#include "idg_device.h"
 
 extern "C" int idg_bpr_touch_rows(const int64_t* users, const int64_t* pos, const int64_t* neg, int64_t B,
                                   int64_t num_users, uint32_t* bitmap, void* stream);
@@ -28,7 +29,10 @@ extern "C" int idg_bpr_touch_rows(const int64_t* users, const int64_t* pos, cons
 namespace {
 
 constexpr int BLOCK = 256;
-constexpr int WAVE = 64;
+using idg::align256;
+using idg::f32x16;
+using idg::WAVE;
+using idg::wave_sum;
 constexpr int TS = 64;  // tile edge of the logits / gradient GEMMs
 constexpr int KC = 16;  // reduction chunk staged in LDS (logits)
 constexpr int GS = 8;   // split-K slices of the gradient products
@@ -54,15 +58,13 @@ struct SslWs {
   size_t bytes;
 };
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
 SslWs ssl_layout(void* base, int64_t n, int64_t B, int64_t d) {
   SslWs w{};
   char* p = reinterpret_cast<char*>(base);
   size_t off = 0;
   auto take = [&](size_t bytes) {
     char* q = p ? p + off : nullptr;
-    off += up256(bytes);
+    off += align256(bytes);
     return q;
   };
   w.bitmap = reinterpret_cast<uint32_t*>(take((size_t)((n + 31) / 32) * 4));
@@ -83,12 +85,6 @@ SslWs ssl_layout(void* base, int64_t n, int64_t B, int64_t d) {
   w.G = reinterpret_cast<float*>(take((size_t)2 * GS * 2 * B * d * 4));
   w.bytes = off;
   return w;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
-  return v;
 }
 
 // ---- bitmap -> ascending id list; ids < num_users form set 0, the rest set 1.  One 1024-thread block.
@@ -423,7 +419,6 @@ __global__ __launch_bounds__(BLOCK) void ssl_grad_kernel(const float* __restrict
 // v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation.  Lane (i, h) feeds row i's K-values [kc + 32h, kc + 32h + 32)
 // as the A operand and column i's as the B operand — one contiguous 128-byte run per lane and 64-deep chunk, nothing
 // staged through LDS; C/D map: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 __device__ __forceinline__ void load32(const float* __restrict__ p, float (&v)[32]) {
 #pragma unroll
@@ -510,7 +505,7 @@ __global__ __launch_bounds__(BLOCK, 2) void ssl_logits_mfma_kernel(const float* 
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = i0 + wr + 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * h, col = k0 + wc + 32 * ct + i;
+        const int row = i0 + wr + 32 * rt + idg::mfma_c_row(r, h), col = k0 + wc + 32 * ct + i;
         if (row < m && col < m) Ps[(int64_t)row * B + col] = expf(acc[rt][ct][r] * inv_t);
       }
 }
@@ -598,7 +593,7 @@ __global__ __launch_bounds__(BLOCK) void ssl_grad_mfma_kernel(const float* __res
   float* out = Gp + (((int64_t)side * GS + slice) * 2 * B + base) * d;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = r0 + tr + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int row = r0 + tr + idg::mfma_c_row(r, h);
     if (row < m) out[(int64_t)row * d + f0 + tf + i] = acc[r];
   }
 }

@@ -32,38 +32,26 @@
 #include <cmath>
 
 #include "idg_common.h"
+#include "idg_tile128.h"
 
 namespace {
 
-constexpr int WAVE = 64;
-constexpr int BLOCK = 256;
-constexpr int T = 128;        // rows of a query / table tile
-constexpr int KC = 32;        // feature chunk of a score tile
-constexpr int LK = KC + 4;    // its LDS row stride (floats): ds_read_b128 of 16 consecutive rows covers all 64 banks
+using namespace idg::tile128;  // T = 128 rows of a query / table tile, LG the row stride of the E / G tile, LDS_FLOATS
+using idg::align256;
+using idg::f32x16;
+using idg::mfma_c_row;
+using idg::round_up;
+using idg::WAVE;
+using idg::wave_sum;
+
 constexpr int MAX_NDT = 8;    // d <= 256
 constexpr int MAX_NQ = IDG_TNCE_MAX_QUERY_BLOCKS;
 constexpr int MAX_CHUNKS = 64;
 constexpr int TARGET_WGS = 512;  // two 80 KB workgroups per CU
 constexpr float NORM_EPS = 1e-12f;
 constexpr float GUARD = 1e-7f;   // the reference's 10e-8
-constexpr int LG = T + 1;     // row stride of the E / G tile: 32 rows of one column, or 32 columns of one row, on 32 banks
-constexpr int LDS_FLOATS = T * LG;  // the E / G tile; the score operands (2 x 128 x LK) alias it: two workgroups per CU
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 enum { MODE_SUMS = 0, MODE_SUMS_ACC = 1, MODE_TABLE = 2 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-  return v;
-}
 
 // Where else does the id of batch position b occur?  One pass over the list with independent loads: (an earlier position
 // holds it, a later one does) — the same on every lane.
@@ -80,9 +68,6 @@ __device__ __forceinline__ void occurrences(const int64_t* __restrict__ ids, int
   earlier = __ballot(e) != 0;
   later = __ballot(l) != 0;
 }
-
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 struct Geo {
   int64_t dp, Np, Bp;
@@ -225,39 +210,7 @@ __global__ __launch_bounds__(BLOCK, NDT <= 4 ? 2 : 1) void tnce_tile_kernel(
     const int64_t y0 = (int64_t)p * T;
     const float* Y = Yall + y0 * dp;
     f32x16 s[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[m][n][r] = 0.f;
-    // ---- S = X Y^T
-    for (int kc = 0; kc < NDT; ++kc) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int e = tid + BLOCK * j, rr = e >> 3, c4 = (e & 7) * 4;
-        *reinterpret_cast<float4*>(s_x + rr * LK + c4) = *reinterpret_cast<const float4*>(X + rr * dp + kc * KC + c4);
-        *reinterpret_cast<float4*>(s_y + rr * LK + c4) = *reinterpret_cast<const float4*>(Y + rr * dp + kc * KC + c4);
-      }
-      __syncthreads();
-      const float* pa = s_x + (64 * wr + i) * LK + 16 * h;
-      const float* pb = s_y + (64 * wc + i) * LK + 16 * h;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float4 a0 = *reinterpret_cast<const float4*>(pa + 4 * c);
-        const float4 a1 = *reinterpret_cast<const float4*>(pa + 32 * LK + 4 * c);
-        const float4 b0 = *reinterpret_cast<const float4*>(pb + 4 * c);
-        const float4 b1 = *reinterpret_cast<const float4*>(pb + 32 * LK + 4 * c);
-#define IDG_TNCE_STEP(F)                                                              \
-  s[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.F, b0.F, s[0][0], 0, 0, 0);       \
-  s[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.F, b1.F, s[0][1], 0, 0, 0);       \
-  s[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.F, b0.F, s[1][0], 0, 0, 0);       \
-  s[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.F, b1.F, s[1][1], 0, 0, 0);
-        IDG_TNCE_STEP(x) IDG_TNCE_STEP(y) IDG_TNCE_STEP(z) IDG_TNCE_STEP(w)
-#undef IDG_TNCE_STEP
-      }
-      __syncthreads();
-    }
+    score_tile_128<NDT>(X, Y, s_x, s_y, s);  // ---- S = X Y^T
     // ---- the E / G^T tile
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
@@ -273,7 +226,7 @@ __global__ __launch_bounds__(BLOCK, NDT <= 4 ? 2 : 1) void tnce_tile_kernel(
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = 64 * wr + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int row = 64 * wr + 32 * m + mfma_c_row(r, h);
           const float e = __builtin_amdgcn_exp2f((s[m][n][r] - 1.f) * scale2);
           float v;
           if (MODE == MODE_TABLE) v = a_b * e;
@@ -316,6 +269,8 @@ __global__ __launch_bounds__(BLOCK, NDT <= 4 ? 2 : 1) void tnce_tile_kernel(
     for (int ct = 0; ct < NDT; ++ct)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
+        // idg::mfma_c_row written out: through the helper the compiler forms these 16 NDT store addresses another way and
+        // the kernels of d = 64 .. 128 take two more registers
         const int row = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h;
         out[(int64_t)row * dp + 32 * ct + i] = acc[ct][r];
       }
@@ -393,13 +348,8 @@ __global__ __launch_bounds__(1024) void tnce_loss_kernel(const float* __restrict
   const int tid = threadIdx.x, k = blockIdx.x;
   float acc = 0.f;
   for (int64_t b = tid; b < B; b += 1024) acc += lrow[(int64_t)k * Bp + b];
-  s[tid] = acc;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (tid < o) s[tid] += s[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) loss[k] = -q.weight[k] * s[0];
+  const float sum = idg::block_tree_sum<1024>(acc, s);
+  if (tid == 0) loss[k] = -q.weight[k] * sum;
 }
 
 // One wave per table row: the dense part sum_b a_b e_bj Qh_b, its splits added in order, back through the normalisation,

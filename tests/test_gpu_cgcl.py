@@ -77,7 +77,9 @@ def _close_grad(mine, ref, tol=1e-5):
 CASES = [(64, 96, 250, 2, 0, 0.1), (128, 96, 63, 1, 5, 0.2), (256, 1, 1, 1, 0, 1.0), (32, 96, 4097, 2, 3, 0.05),
          (48, 2048, 250, 1, 0, 0.1), (100, 96, 4097, 2, 7, 0.2), (64, 2048, 38048, 2, 100, 0.1), (256, 96, 4097, 1, 0, 0.1),
          (128, 1, 63, 2, 0, 1.0), (48, 1, 38048, 1, 0, 0.05), (100, 2048, 1, 1, 2, 0.2), (32, 2048, 63, 2, 0, 1.0),
-         (64, 96, 128, 1, 0, 0.05), (64, 128, 129, 2, 1, 0.1)]
+         (64, 96, 128, 1, 0, 0.05), (64, 128, 129, 2, 1, 0.1),
+         # the widths of 3, 5, 6 and 7 feature chunks (the score loop is unrolled up to 5 chunks and rolled above)
+         (96, 96, 250, 2, 0, 0.1), (160, 96, 129, 1, 3, 0.2), (192, 1, 63, 1, 0, 1.0), (224, 96, 250, 2, 0, 0.1)]
 
 
 @pytest.mark.parametrize("d,B,N,nq,row0,tau", CASES)

@@ -21,7 +21,9 @@ STRONG = dict(ssl_lambda=0.1, proto_lambda=1e-3, alpha=0.6)
 # 100 and the widest; K split over workgroups (few row tiles) with a partial last tile; rows of the magnitude of a
 # Xavier-initialised table
 CASES = [(1, 1, 64, 1.0), (127, 2, 32, 1.0), (129, 127, 256, 1.0), (500, 16, 64, 1.0), (4097, 129, 48, 1.0),
-         (4097, 2000, 64, 1.0), (4097, 2000, 100, 1.0), (900, 40, 64, 0.02)]
+         (4097, 2000, 64, 1.0), (4097, 2000, 100, 1.0), (900, 40, 64, 0.02),
+         # the widths of 3, 5, 6 and 7 feature chunks (the score loop is unrolled up to 5 chunks and rolled above)
+         (129, 127, 96, 1.0), (129, 127, 160, 1.0), (500, 16, 192, 1.0), (129, 127, 224, 1.0)]
 
 
 @pytest.fixture(scope="module")
