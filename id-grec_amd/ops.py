@@ -284,17 +284,23 @@ class Graph:
     # ---- raw (non-autograd) calls
     def spmm_raw(self, X, addend=None, out=None):
         _require_device(X, addend, out)
-        X = _f32c(X, "X")
+        # a column slice of a wider contiguous panel (row stride ldx, unit column stride) is read where it lies:
+        # idg_spmm_f32 takes the leading dimension (LR-GCCF's layers live only in their slots of the final panel)
+        in_place = X.dim() == 2 and X.dtype == torch.float32 and not X.is_contiguous() and X.stride(1) == 1 \
+            and X.stride(0) >= X.shape[1]
+        if not in_place:
+            X = _f32c(X, "X")
         if X.dim() != 2 or X.shape[0] != self.n_cols:
             raise ValueError("X must be [%d, d], got %s" % (self.n_cols, tuple(X.shape)))
         d = X.shape[1]
+        ldx = X.stride(0) if in_place else d
         Y = torch.empty((self.n_rows, d), dtype=torch.float32, device=X.device) if out is None else out
         if addend is not None:
             addend = _f32c(addend, "addend")
             if addend.shape != Y.shape:
                 raise ValueError("addend shape %s != output shape %s" % (tuple(addend.shape), tuple(Y.shape)))
         ws = self._workspace("spmm", d)
-        check(lib.idg_spmm_f32(self._h, _ptr(X), d, _ptr(Y), d, _ptr(addend), d, _ptr(ws), _stream()), "idg_spmm_f32")
+        check(lib.idg_spmm_f32(self._h, _ptr(X), ldx, _ptr(Y), d, _ptr(addend), d, _ptr(ws), _stream()), "idg_spmm_f32")
         return Y
 
     def propagate_mean_raw(self, E0, K, include_layer0=True, out=None, out_rows=None):
@@ -1260,6 +1266,84 @@ def ngcf_layer_tail(S1, S2, b1, b2, negative_slope=0.2, p=0.0, stream=None):
     S2 = None: S1 already holds their sum (ngcf_transform).
     stream: (seed, stream id) of the dropout mask; default: the next one of the device seed's sequence."""
     return _NgcfTail.apply(S1, S2, b1, b2, negative_slope, p, _next_noise_stream() if stream is None else stream)
+
+
+# ----------------------------------------------------------------------------------- LR-GCCF's linear layer
+_gccf_ws = {}
+
+
+def gccf_layer_fwd_raw(side, W, b, p, seed, stream_id, E, lde=None, slot=0):
+    """idg_gccf_layer_fwd_f32: E[r, 0:64] = keep * (side[r] . W + b), written `slot` floats into each row of E with leading
+    dimension lde (default: E's own width)."""
+    _require_device(side, W, b, E)
+    n, d = side.shape
+    check(lib.idg_gccf_layer_fwd_f32(_ptr(side), _ptr(W), _ptr(b), n, d, float(p), C.c_uint64(seed), C.c_uint64(stream_id),
+                                     E.data_ptr() + 4 * int(slot), int(E.shape[1] if lde is None else lde), _stream()),
+          "idg_gccf_layer_fwd_f32")
+    return E
+
+
+def gccf_layer_bwd_raw(gE, gN, ldgn, gn_rows, side, W, p, seed, stream_id, g_side, w_grads, gn_slot=0):
+    """idg_gccf_layer_bwd_f32: gT = keep * (gE + gN at the rows of the bitmap gn_rows); g_side = gT . W^T;
+    w_grads = [side^T . gT | column sums of gT].  gN is read `gn_slot` floats into each row, leading dimension ldgn."""
+    _require_device(gE, gN, gn_rows, side, W, g_side, w_grads)
+    n, d = side.shape
+    ws = _gccf_ws.get((d, side.device))
+    if ws is None:
+        ws = _gccf_ws[(d, side.device)] = torch.empty(max(int(lib.idg_gccf_layer_bwd_workspace_bytes(d)), 16), dtype=torch.uint8,
+                                                      device=side.device)
+    check(lib.idg_gccf_layer_bwd_f32(_ptr(gE), None if gN is None else gN.data_ptr() + 4 * int(gn_slot), int(ldgn), _ptr(gn_rows),
+                                     _ptr(side), _ptr(W), n, d, float(p), C.c_uint64(seed), C.c_uint64(stream_id), _ptr(g_side),
+                                     _ptr(w_grads), _ptr(ws), _stream()), "idg_gccf_layer_bwd_f32")
+    return g_side, w_grads
+
+
+class _GccfLayer(torch.autograd.Function):
+    """E = dropout(side @ W + b) at d = 64 in one kernel per direction (csrc/idg_gccf.hip).  The backward needs no saved
+    activation: the mask is regenerated from (seed, stream id), and the layer is linear in between."""
+
+    @staticmethod
+    def forward(ctx, side, W, b, p, stream):
+        seed, sid = stream
+        E = torch.empty_like(side)
+        gccf_layer_fwd_raw(side, W, b.reshape(-1), p, seed, sid, E)
+        ctx.save_for_backward(side, W)
+        ctx.args = (float(p), seed, sid, b.shape)
+        return E
+
+    @staticmethod
+    def backward(ctx, gE):
+        side, W = ctx.saved_tensors
+        p, seed, sid, b_shape = ctx.args
+        d = W.shape[0]
+        g_side = torch.empty_like(side)
+        w_grads = torch.empty(d * d + d, dtype=torch.float32, device=side.device)
+        gccf_layer_bwd_raw(_f32c(gE, "gE"), None, d, None, side, W, p, seed, sid, g_side, w_grads)
+        return g_side, w_grads[:d * d].view(d, d), w_grads[d * d:].view(b_shape), None, None
+
+
+def gccf_layer(side, W, b, p, stream=None):
+    """One LR-GCCF layer after the sparse product: nn.Dropout(p)(torch.matmul(side, W) + b) (Chen et al., AAAI'20).
+    side [n, d1], W [d1, d2], b [1, d2] or [d2].  d1 = d2 = 64: idg_gccf_layer_fwd_f32 / idg_gccf_layer_bwd_f32; any other
+    width: tall_linear and ngcf_layer_tail with slope 1 and a zero second bias, whose first output is exactly
+    dropout(S + b).  stream: (seed, stream id) of the dropout mask; default: the next one of the device seed's sequence."""
+    for t, name in ((side, "side"), (W, "W"), (b, "b")):
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be float32 (got %s)" % (name, t.dtype))
+    if side.dim() != 2 or W.dim() != 2:
+        raise ValueError("gccf_layer: side must be [n, d] and W [d, d2], got %s and %s" % (tuple(side.shape), tuple(W.shape)))
+    if side.shape[1] != W.shape[0] or b.numel() != W.shape[1]:
+        raise ValueError("gccf_layer: side %s, W %s and b %s do not fit (side [n, d], W [d, d2], b [1, d2])"
+                         % (tuple(side.shape), tuple(W.shape), tuple(b.shape)))
+    if side.shape[0] == 0:
+        raise ValueError("gccf_layer: side has 0 rows")
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError("gccf_layer: drop probability p = %g outside [0, 1)" % float(p))
+    _require_device(side, W, b)
+    stream = _next_noise_stream() if stream is None else stream
+    if tuple(W.shape) == (64, 64):
+        return _GccfLayer.apply(_f32c(side, "side"), _f32c(W, "W"), _f32c(b, "b"), float(p), stream)
+    return ngcf_layer_tail(tall_linear(side, W), None, b, torch.zeros_like(b), 1.0, float(p), stream)[0]
 
 
 # ----------------------------------------------------------------------------------- InfoNCE

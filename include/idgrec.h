@@ -565,6 +565,23 @@ int idg_ngcf_layer_bwd_f32(const float* E, const float* gE, const float* gN, int
                            const float* side, const float* ego, const float* W1, const float* W2, int64_t n, int64_t d,
                            float negative_slope, float p, uint64_t seed, uint64_t stream_id, float* g_side, float* g_ego,
                            float* w_grads, void* ws, void* stream);
+/* One LR-GCCF layer (E = dropout(side . W + b); no bilinear term, no activation, no row norm) as ONE kernel per direction,
+ * d = 64 (csrc/idg_gccf.hip).  The mask is idg_ngcf_tail_f32's published function of (seed, stream_id, row, feature).
+ *   forward : E[r, 0:d] = keep(r, .) * (side[r, .] . W + b), E written with leading dimension lde (layer l's slot of the
+ *             concatenated final rows); bytes outside columns 0 .. d-1 of a row, and rows >= n, are not touched;
+ *   backward: gT = keep * ((gE or 0) + (gN at the rows flagged in gn_rows, read with ldgn)); gn_rows = NULL: every row;
+ *             what gN holds off the flagged rows is never read; at least one of gE, gN must be given.  No saved activation
+ *             is needed.  g_side = gT . W^T [n, 64];  w_grads = [gW (64 x 64) = side^T . gT | gb (64) = column sums of gT].
+ * The sums over rows run in a fixed order (slices of rows on persistent workgroups, added in slice order): two runs give
+ * the same bits.  Any other d, NULL or misaligned pointers (panels and, in the backward, W: 16 bytes), n <= 0, a leading
+ * dimension below d or not a multiple of 4, p outside [0, 1) and outputs that overlap inputs: IDG_E_INVALID before any
+ * device work.  ws: as many bytes as idg_gccf_layer_bwd_workspace_bytes returns for d (0 for a width that is not built). */
+int idg_gccf_layer_fwd_f32(const float* side, const float* W, const float* b, int64_t n, int64_t d, float p, uint64_t seed,
+                           uint64_t stream_id, float* E, int64_t lde, void* stream);
+size_t idg_gccf_layer_bwd_workspace_bytes(int64_t d);
+int idg_gccf_layer_bwd_f32(const float* gE, const float* gN, int64_t ldgn, const uint32_t* gn_rows, const float* side,
+                           const float* W, int64_t n, int64_t d, float p, uint64_t seed, uint64_t stream_id, float* g_side,
+                           float* w_grads, void* ws, void* stream);
 /* Glue of that step.  idg_copy_cols_f32: dst[r, 0:d] = src[r, 0:d] with leading dimensions ldd / lds.  idg_rows_add2_f32:
  * dst[r] += a[r] (+ b[r]) at the rows flagged in `rows`.  idg_colsum_f32: out[f] (+)= sum over the n rows of X[r, f] — the
  * gradient of a bias row broadcast over n rows (the differentiable layer tail's backward; the fused step gets it from
