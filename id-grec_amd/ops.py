@@ -1346,6 +1346,118 @@ def gccf_layer(side, W, b, p, stream=None):
     return ngcf_layer_tail(tall_linear(side, W), None, b, torch.zeros_like(b), 1.0, float(p), stream)[0]
 
 
+# ----------------------------------------------------------------------------------- BIGCF's intent layer
+_intent_ws = {}
+
+
+def _ld(t):
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def _row_base(t, base_row):
+    """Pointer of GLOBAL row 0 of a panel whose first row is global row base_row (never dereferenced below that row)."""
+    return None if t is None else t.data_ptr() - 4 * int(base_row) * _ld(t)
+
+
+def intent_noise_raw(out, seed, stream_id, base_row=0):
+    """idg_intent_noise_f32: out[r, f] = the normal of (seed, stream_id, base_row + r, f) — the Z the intent kernels generate,
+    at any width (the composed path of intent_mix draws it here)."""
+    _require_device(out)
+    n, d = out.shape
+    check(lib.idg_intent_noise_f32(int(base_row), n, d, C.c_uint64(seed), C.c_uint64(stream_id), _row_base(out, base_row), _stream()),
+          "idg_intent_noise_f32")
+    return out
+
+
+def intent_fwd_raw(X, W, T, F, row0=0, nrows=None, rows_bitmap=None, noise=None, seed=0, stream_id=0, noise_out=None, base_row=0):
+    """idg_intent_fwd_f32 on global rows row0 .. row0 + nrows - 1: T = softmax(X . W) . W^T, F = X + T o Z.  The panels'
+    first row is global row base_row (default 0: whole panels; row0 >= base_row); rows_bitmap is indexed by the global row.
+    Leading dimensions are the tensors' row strides; noise / noise_out are contiguous [., d]."""
+    _require_device(X, W, T, F, rows_bitmap, noise, noise_out)
+    d, k = W.shape
+    nrows = X.shape[0] - (int(row0) - int(base_row)) if nrows is None else nrows
+    check(lib.idg_intent_fwd_f32(_row_base(X, base_row), _ld(X), int(row0), int(nrows), _ptr(W), d, k, _ptr(rows_bitmap),
+                                 _row_base(noise, base_row), C.c_uint64(seed), C.c_uint64(stream_id), _row_base(T, base_row), _ld(T),
+                                 _row_base(F, base_row), _ld(F), _row_base(noise_out, base_row), _stream()), "idg_intent_fwd_f32")
+    return F, T
+
+
+def intent_bwd_raw(gF, gT_in, rows_bitmap, X, W, gX, gW, row0=0, nrows=None, noise=None, seed=0, stream_id=0, base_row=0, ws=None,
+                   gt_rows=None):
+    """idg_intent_bwd_f32 on global rows row0 .. row0 + nrows - 1 (flagged rows only when rows_bitmap is given):
+    gX = gF + gS . W^T, gW = X^T . gS + gT^T . P with gT = gT_in (at the rows of gt_rows, when given) + gF o Z; P and Z are
+    recomputed."""
+    _require_device(gF, gT_in, rows_bitmap, X, W, gX, gW, noise, gt_rows)
+    d, k = W.shape
+    nrows = X.shape[0] - (int(row0) - int(base_row)) if nrows is None else nrows
+    if ws is None:
+        ws = _intent_ws.get((d, k, X.device))
+        if ws is None:
+            ws = _intent_ws[(d, k, X.device)] = torch.empty(max(int(lib.idg_intent_bwd_workspace_bytes(d, k)), 16), dtype=torch.uint8,
+                                                           device=X.device)
+    check(lib.idg_intent_bwd_f32(_row_base(gF, base_row), _ld(gF), _row_base(gT_in, base_row), 0 if gT_in is None else _ld(gT_in),
+                                 _ptr(gt_rows), _ptr(rows_bitmap), _row_base(X, base_row), _ld(X), int(row0), int(nrows), _ptr(W), d, k,
+                                 _row_base(noise, base_row), C.c_uint64(seed), C.c_uint64(stream_id), _row_base(gX, base_row), _ld(gX),
+                                 _ptr(gW), _ptr(ws), _stream()), "idg_intent_bwd_f32")
+    return gX, gW
+
+
+class _IntentMix(torch.autograd.Function):
+    """(F, T) of the intent layer at (d, k) = (64, 128) in one kernel per direction (csrc/idg_intent.hip).  Saved: X, W (and
+    the noise panel when one was passed in); P is recomputed and Z regenerated from (seed, stream id, global row)."""
+
+    @staticmethod
+    def forward(ctx, X, W, row0, stream, noise):
+        seed, sid = stream
+        F, T = torch.empty_like(X), torch.empty_like(X)
+        intent_fwd_raw(X, W, T, F, row0=row0, noise=noise, seed=seed, stream_id=sid, base_row=row0)
+        ctx.save_for_backward(X, W, noise)
+        ctx.args = (int(row0), seed, sid)
+        return F, T
+
+    @staticmethod
+    def backward(ctx, gF, gT):
+        X, W, noise = ctx.saved_tensors
+        row0, seed, sid = ctx.args
+        gF = torch.zeros_like(X) if gF is None else _f32c(gF, "gF")
+        gT = None if gT is None else _f32c(gT, "gT")
+        gX, gW = torch.empty_like(X), torch.empty_like(W)
+        intent_bwd_raw(gF, gT, None, X, W, gX, gW, row0=row0, noise=noise, seed=seed, stream_id=sid, base_row=row0)
+        return gX, gW, None, None, None
+
+
+def intent_mix(X, W, row0=0, stream=None, noise=None):
+    """BIGCF's intent layer (models/BIGCF.py:62-69) on the rows of X [n, d] with the intent matrix W [d, k]:
+    T = softmax(X @ W, dim=1) @ W.T, F = X + T * Z; returns (F, T), differentiable in X and W.  Z ~ N(0, 1): `noise` [n, d]
+    when given, else the counter-based normal of (seed, stream id, row0 + r, f) — row0 is the global row of X's first row,
+    so the user and the item rows of one panel draw different noise from one stream.  (d, k) = (64, 128):
+    idg_intent_fwd_f32 / idg_intent_bwd_f32; any other width composes torch operators with the same Z
+    (idg_intent_noise_f32).  stream: (seed, stream id); default: the next one of the device seed's sequence."""
+    for t, name in ((X, "X"), (W, "W"), (noise, "noise")):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("intent_mix: %s must be float32 (got %s)" % (name, t.dtype))
+    if X.dim() != 2 or W.dim() != 2:
+        raise ValueError("intent_mix: X must be [n, d] and W [d, k], got %s and %s" % (tuple(X.shape), tuple(W.shape)))
+    if X.shape[1] != W.shape[0]:
+        raise ValueError("intent_mix: X %s and W %s do not fit (X [n, d], W [d, k])" % (tuple(X.shape), tuple(W.shape)))
+    if X.shape[0] == 0:
+        raise ValueError("intent_mix: X has 0 rows")
+    if noise is not None and tuple(noise.shape) != tuple(X.shape):
+        raise ValueError("intent_mix: noise %s must have X's shape %s" % (tuple(noise.shape), tuple(X.shape)))
+    if int(row0) < 0:
+        raise ValueError("intent_mix: row0 = %d is negative" % int(row0))
+    if not (X.is_cuda and W.is_cuda and (noise is None or noise.is_cuda)):
+        raise RuntimeError("intent_mix: runs on MI355X only (got X on %s, W on %s); there is no CPU fallback" % (X.device, W.device))
+    stream = _next_noise_stream() if stream is None else stream
+    noise = None if noise is None else _f32c(noise.detach(), "noise")
+    if tuple(W.shape) == (64, 128):
+        return _IntentMix.apply(_f32c(X, "X"), _f32c(W, "W"), int(row0), stream, noise)
+    if noise is None:
+        noise = intent_noise_raw(torch.empty(tuple(X.shape), dtype=torch.float32, device=X.device), stream[0], stream[1], base_row=row0)
+    T = torch.softmax(X @ W, dim=1) @ W.t()
+    return X + T * noise, T
+
+
 # ----------------------------------------------------------------------------------- InfoNCE
 
 

@@ -591,6 +591,31 @@ int idg_colsum_f32(const float* X, int64_t ldx, int64_t n, int64_t d, float* out
 int idg_copy_cols_f32(float* dst, int64_t ldd, const float* src, int64_t lds, int64_t n, int64_t d, void* stream);
 int idg_rows_add2_f32(float* dst, int64_t ldd, const float* a, int64_t lda, const float* b, int64_t ldb,
                       const uint32_t* rows, int64_t n, int64_t d, void* stream);
+/* BIGCF's intent layer on rows row0 .. row0 + nrows - 1 of a panel (models/BIGCF.py:62-69; csrc/idg_intent.hip), one kernel
+ * per direction, (d, k) = (64, 128), fp32:  S = X . W [., k],  P = softmax(S) (row maximum subtracted),  T = P . W^T,
+ * F = X + T o Z.  Every panel, the bitmap and the noise are indexed by the GLOBAL row (the pointers are those of row 0);
+ * row0 need not be a multiple of the 64-row tile.  Z = `noise`[row, feature] (a contiguous [., d] panel) when given, else
+ * idg_vae_head_fwd_f32's published normal of (seed, stream_id, row, feature); noise_out (nullable, [., d]) receives the Z
+ * that was used.  rows_bitmap (nullable = every row): a row whose bit is clear is neither read nor written, a tile with no
+ * flagged row is skipped.
+ *   backward: gT = (gT_in or 0) + gF o Z [never stored]; gt_rows (nullable = wherever rows_bitmap allows): gT_in is read at
+ *             the flagged rows whose bit of gt_rows is set too, and counts as zero at the others (a training step's gT lives
+ *             on the user and positive rows, its gF on the negative rows as well);  gP = gT . W;  gS = P o (gP - rowsum(P o gP));
+ *             gX = gF + gS . W^T (written at the flagged rows only);  gW [d, k] = X^T . gS + gT^T . P (stored, not added).
+ * P is recomputed from X and W and Z regenerated: no activation is saved.  gW is summed in a fixed order (row slices on
+ * persistent workgroups, added in slice order): two runs give the same bits.  Any other (d, k), NULL or misaligned pointers
+ * (panels and W: 16 bytes), nrows <= 0, row0 < 0, a leading dimension below d or not a multiple of 4 and outputs that
+ * overlap inputs or each other: IDG_E_INVALID before any device work.  ws: as many bytes as idg_intent_bwd_workspace_bytes
+ * returns for the widths (0 for widths that are not built).  idg_intent_noise_f32: that Z alone, noise_out[row, f] for rows row0 .. row0 + nrows - 1 of
+ * a contiguous [., d] panel of ANY width d (the composed path of other widths draws the same noise). */
+int idg_intent_noise_f32(int64_t row0, int64_t nrows, int64_t d, uint64_t seed, uint64_t stream_id, float* noise_out, void* stream);
+int idg_intent_fwd_f32(const float* X, int64_t ldx, int64_t row0, int64_t nrows, const float* W, int64_t d, int64_t k,
+                       const uint32_t* rows_bitmap, const float* noise, uint64_t seed, uint64_t stream_id, float* T, int64_t ldt,
+                       float* F, int64_t ldf, float* noise_out, void* stream);
+size_t idg_intent_bwd_workspace_bytes(int64_t d, int64_t k);
+int idg_intent_bwd_f32(const float* gF, int64_t ldgf, const float* gT_in, int64_t ldgt, const uint32_t* gt_rows,
+                       const uint32_t* rows_bitmap, const float* X, int64_t ldx, int64_t row0, int64_t nrows, const float* W, int64_t d, int64_t k, const float* noise,
+                       uint64_t seed, uint64_t stream_id, float* gX, int64_t ldgx, float* gW, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * DEVICE: in-batch InfoNCE between two views, forward + backward
