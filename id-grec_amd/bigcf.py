@@ -1,6 +1,6 @@
 """Fused, autograd-free training step of BIGCF (Zhang et al., SIGIR'24; reference: models/BIGCF.py:46-106 +
-utility/utility_train/trainer.py:42-56) as a fixed chain of C-ABI calls on preallocated panels, in the pattern of
-idgrec_amd/gccf.py and idgrec_amd/egcf.py.  d = 64, intent_size = 128.
+utility/utility_train/trainer.py:42-56) as a fixed chain of C-ABI calls on preallocated panels: a
+PanelEngine (idgrec_amd/engine.py) whose InfoNCE id lists are planned as EgcfEngine's are.  d = 64, intent_size = 128.
 
 Forward (n = U + I rows, users first; P = the packed [n, d] embedding panel, G = the symmetric normalised adjacency):
     X = G P + G^2 P + .. + G^K P                            idg_spmm_ex_f32, the running sum in the products' epilogues
@@ -20,73 +20,55 @@ rows (a second bitmap of the slot: a negative's row has a gF but no gT, and what
 No dense panel is zeroed or restored: every reader of gF, gT, gX and GE is restricted to the batch's rows, so nothing an
 earlier step left off them is seen (tests/test_gpu_bigcf.py runs two steps with different batches to hold that).
 
-W_u and W_i live in ONE flat buffer [W_u | W_i] (views handed back to the nn.Parameters), as do their gradients — the two
-backward calls write straight into their places — and both Adam moments: one Adam launch for both, after the regulariser's
-reg_lambda W / d has joined the gradient."""
-import ctypes as C
-
+W_u and W_i are the two groups of PanelEngine's flat buffer, [W_u | W_i]: the two backward calls write their gradients
+straight into their places, and the one Adam launch for both follows after the regulariser's reg_lambda W / d has joined the
+gradient."""
 import torch
 
 from . import native, ops
-from .engine import BatchPrep
+from .engine import BatchPrep, PanelEngine, plan_infonce
 
-lib, check = native.lib, native.check
+lib = native.lib
 
 
-class BigcfEngine:
+class BigcfEngine(PanelEngine):
     def __init__(self, graph, num_users, num_items, params, intents, n_layers, reg_lambda=1e-4, ssl_lambda=0.2, temperature=0.2,
                  lr=1e-3, betas=(0.9, 0.999), eps=1e-8, store_grad=False):
         """params: the packed [n, 64] embedding panel (users first; updated in place).  intents: (W_u, W_i), [64, 128] each —
         copied into this engine's flat buffer; intent_views() returns the views to re-point the nn.Parameters at."""
-        self.G = graph
-        self.U, self.I = int(num_users), int(num_items)
-        self.n, self.d = int(params.shape[0]), int(params.shape[1])
-        self.K = int(n_layers)
-        assert self.n == self.U + self.I and params.is_cuda and params.is_contiguous()
-        n, d = self.n, self.d
-        self.k = k = int(intents[0].shape[1])
+        d, k = int(params.shape[1]), int(intents[0].shape[1])
         if (d, k) != (64, 128) or any(tuple(w.shape) != (d, k) for w in intents):
             raise ValueError("BigcfEngine: (embedding_size, intent_size) = (64, 128) only (got %s); other widths train through "
                              "the differentiable operators" % (tuple(intents[0].shape),))
-        if self.K < 1:
+        if int(n_layers) < 1:
             raise ValueError("BigcfEngine: GCN_layer >= 1 (the ego layer is not part of BIGCF's rows)")
-        self.reg_lambda, self.ssl_lambda, self.temperature = float(reg_lambda), float(ssl_lambda), float(temperature)
-        self.lr, self.betas, self.eps = float(lr), betas, float(eps)
-        self.store_grad = bool(store_grad)
-        dev = params.device
-        self.device = dev
+        # two groups of one: [W_u | W_i].  loss: [bpr, reg_lambda * reg, ssl_lambda * (five InfoNCE terms)]
+        super().__init__(graph, num_users, num_items, params, [(w,) for w in intents], 3, reg_lambda, lr, betas, eps, store_grad)
+        self.K, self.k = int(n_layers), k
+        self.ssl_lambda, self.temperature = float(ssl_lambda), float(temperature)
+        n, dev = self.n, self.device
         f32 = dict(dtype=torch.float32, device=dev)
-        self.P = params
-        per = self._per = d * k
-        self.SW, self.SG = torch.empty(2 * per, **f32), torch.zeros(2 * per, **f32)
-        self.SM, self.SV = torch.zeros(2 * per, **f32), torch.zeros(2 * per, **f32)
-        self._views = tuple(self.SW[i * per:(i + 1) * per].view(d, k) for i in range(2))
-        self._gviews = tuple(self.SG[i * per:(i + 1) * per].view(d, k) for i in range(2))
-        for v, w in zip(self._views, intents):
-            v.copy_(w)
+        self._W = tuple(g[0] for g in self._views)    # (W_u, W_i)
+        self._GW = tuple(g[0] for g in self._gviews)  # their gradients
         panel = lambda: torch.empty((n, d), **f32)  # noqa: E731
         self.E = [panel() for _ in range(min(self.K - 1, 2))]  # layer ping-pong (K >= 2)
         self.S = panel() if self.K > 2 else None               # running layer sum (K >= 3)
         self.X, self.F, self.T = panel(), panel(), panel()
         self.GF, self.GT, self.GE, self.GX = panel(), panel(), panel(), panel()
         self.H = [panel() for _ in range(min(self.K - 1, 2))]  # the backward chain's ping-pong
-        self.GRAD = panel()
-        self.M, self.V = torch.zeros((n, d), **f32), torch.zeros((n, d), **f32)
         # the batch's row bitmap, its live units and scatter plan, the InfoNCE id lists and the (users, positives) bitmap:
         # side stream, one batch ahead
         self.prep = BatchPrep(self.U, n, d, dev, units_graph=graph, extra=self._plan_extra)
         self.ws = torch.empty(int(lib.idg_intent_bwd_workspace_bytes(d, k)), dtype=torch.uint8, device=dev)
-        self.loss = torch.zeros(3, **f32)  # [bpr, reg_lambda * reg, ssl_lambda * (five InfoNCE terms)]
         self._ssl = torch.zeros(6, **f32)  # F: user-user, pos-pos; T: user-user, pos-pos; F: user-pos (+ pad)
         self._wreg = torch.zeros(1, **f32)
-        self.step_count = 0
         self._stream = None
 
     def intent_views(self):
-        return self._views
+        return self._W
 
     def intent_grads(self):
-        return self._gviews
+        return self._GW
 
     # ---- forward (every row): X, then (F, T) with the noise of `stream` = (seed, stream id), or of the panel `noise`
     @torch.no_grad()
@@ -104,7 +86,7 @@ class BigcfEngine:
             prev = cur
         self._stream = stream if stream is not None else ops._next_noise_stream()
         seed, sid = self._stream
-        for row0, nrows, w in ((0, U, self._views[0]), (U, n - U, self._views[1])):
+        for row0, nrows, w in ((0, U, self._W[0]), (U, n - U, self._W[1])):
             ops.intent_fwd_raw(self.X, w, self.T, self.F, row0=row0, nrows=nrows, noise=noise, seed=seed, stream_id=sid)
         return self.F, self.T
 
@@ -112,17 +94,12 @@ class BigcfEngine:
     @torch.no_grad()
     def train_step(self, users, pos, neg, loss_out=None, stream=None, noise=None):
         n, d, K, U = self.n, self.d, self.K, self.U
-        p_ = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        st = ops._stream()
-        B = int(users.shape[0])
         loss = self.loss if loss_out is None else loss_out
         slot = self.prep.take(users, pos, neg)
         bitmap = slot.bitmap
         self.forward(stream, noise)
         seed, sid = self._stream
-        check(lib.idg_bpr_fused_ex_f32(p_(self.F), d, p_(self.P), d, U, n, p_(users), p_(pos), p_(neg), B, self.reg_lambda, 1,
-                                       p_(loss), p_(self.GF), p_(self.GE), native.IDG_BPR_PLANNED | native.IDG_BPR_TOUCHED_PRESET,
-                                       p_(bitmap), p_(slot.ws), st), "idg_bpr_fused_ex_f32")
+        self._bpr(self.F, d, users, pos, neg, 1, loss, self.GF, slot)
         # the self-contrast terms: both arguments are the SAME rows, so the call takes one panel as both views and one
         # gradient panel as both gradients (idg_infonce_pair_f32 adds view 1's and view 2's rows into it, view 1 first)
         t, lam = self.temperature, self.ssl_lambda
@@ -135,7 +112,7 @@ class BigcfEngine:
         torch.sum(self._ssl[:5], dim=0, keepdim=True, out=loss[2:3])
         loss[2:3].mul_(lam)
         for i, (row0, nrows) in enumerate(((0, U), (U, n - U))):
-            ops.intent_bwd_raw(self.GF, self.GT, bitmap, self.X, self._views[i], self.GX, self._gviews[i], row0=row0, nrows=nrows,
+            ops.intent_bwd_raw(self.GF, self.GT, bitmap, self.X, self._W[i], self.GX, self._GW[i], row0=row0, nrows=nrows,
                                noise=noise, seed=seed, stream_id=sid, ws=self.ws, gt_rows=slot.up_bitmap)
         # d loss / d P = G (gX + G (gX + ..)) + GE: gX lives on the batch's rows, the first product reads only those
         self.step_count += 1
@@ -144,7 +121,7 @@ class BigcfEngine:
             nxt = self.H[(l - 1) & 1]
             ops.spmm_epi_raw(self.G, h, Y=nxt, addend=self.GX, mask=bitmap, x_rows=x_rows)
             h, x_rows = nxt, None
-        adam = (self.P, self.M, self.V, self.lr, self.step_count, self.betas[0], self.betas[1], self.eps)
+        adam = self._adam()
         if K == 1:
             # the only product reads gX, which exists at the batch's rows alone: the row-restricted launch, which has no Adam
             # epilogue — the finished gradient is stored and the dense Adam launch follows
@@ -158,7 +135,7 @@ class BigcfEngine:
         self._wreg.copy_(torch.dot(self.SW, self.SW))
         loss[1:2].add_(self._wreg, alpha=0.5 * c)
         ops.lincomb_raw(self.SG, self.SG, 1.0, self.SW, c)
-        ops.adam_step_raw(self.SW, self.SG, self.SM, self.SV, self.lr, self.step_count, self.betas[0], self.betas[1], self.eps)
+        self._adam_small()
         self.prep.release(slot)
         return loss
 
@@ -166,16 +143,7 @@ class BigcfEngine:
         """BatchPrep's hook: the id-list stages of the step's InfoNCE calls (raw user / item lists — shared by the self terms on
         F and on T — and the cross form), each into a workspace of the slot's own, and the bitmap of the user and positive
         rows (where gT lives)."""
-        B = int(users.shape[0])
-        if getattr(slot, "ssl_B", -1) != B:
-            slot.ssl_ws = (ops.infonce_workspace(self.n, B, self.d, self.device), ops.infonce_workspace(self.n, B, self.d, self.device))
-            slot.ssl_B = B
+        plan_infonce(slot, users, pos, self.U, self.n, self.d, self.device, stream)
         if getattr(slot, "up_bitmap", None) is None:
             slot.up_bitmap = torch.zeros((self.n + 31) // 32, dtype=torch.int32, device=self.device)
-        ops.infonce_plan_raw(users, pos, self.U, self.n, self.d, ops.SSL_RAW, slot.ssl_ws[0], stream=stream)
-        ops.infonce_plan_raw(users, pos, self.U, self.n, self.d, ops.SSL_CROSS, slot.ssl_ws[1], stream=stream)
         ops.bpr_touch_rows_raw(users, pos, pos, self.U, slot.up_bitmap, stream=stream, clear_bits=self.n)
-
-    def prefetch(self, users, pos, neg):
-        """One-batch lookahead of the index-only work of the NEXT step (side stream)."""
-        self.prep.prefetch(users, pos, neg)

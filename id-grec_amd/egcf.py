@@ -18,7 +18,7 @@ No torch arithmetic runs in a step (the three InfoNCE losses are summed by a 3-e
 import torch
 
 from . import native, ops
-from .engine import BatchPrep
+from .engine import BatchPrep, plan_infonce
 
 
 class EgcfEngine:
@@ -64,6 +64,14 @@ class EgcfEngine:
         """The parameter storage ([I, d] view): what nn.Embedding.weight aliases."""
         return self.EGO[self.U:]
 
+    def param_views(self):
+        """Where the parameters live, in moment_homes()'s order: the item table alone."""
+        return [self.item_table()]
+
+    def moment_homes(self):
+        """(exp_avg, exp_avg_sq) of the item table: what modeling.adopt_adam_state makes an optimizer's state entries be."""
+        return [(self.M, self.V)]
+
     # ---- forward over every row (evaluation): returns (users, items) views of TOT
     @torch.no_grad()
     def propagate(self, out_rows=None):
@@ -94,7 +102,7 @@ class EgcfEngine:
         # prefetch() during the previous step, or right now
         slot = self.prep.take(users, pos, neg)
         bitmap = slot.bitmap
-        self.propagate(out_rows=bitmap)
+        self._propagate_for_step(slot)
         # losses: gradient rows STORED at the batch's rows (bitmap), the InfoNCE terms added into the same rows
         ops.bpr_fused_raw(self.TOT, self.EGO, users, pos, neg, U, self.reg_lambda, self.GT, self.GE, loss=loss[:2],
                           deterministic=2 | native.IDG_BPR_TOUCHED_PRESET, touched=bitmap, ws=slot.ws)
@@ -108,6 +116,10 @@ class EgcfEngine:
         self._backward(slot, bitmap)
         self.prep.release(slot)
         return loss
+
+    def _propagate_for_step(self, slot):
+        """The step's forward: the last layer and TOT at the batch's rows only."""
+        self.propagate(out_rows=slot.bitmap)
 
     def _backward(self, slot, bitmap):
         U, K, X = self.U, self.K, self.X
@@ -129,12 +141,7 @@ class EgcfEngine:
     def _plan_ssl(self, slot, users, pos, neg, stream):
         """BatchPrep's hook: the id-list stages of the step's two InfoNCE calls (raw user / item lists; the cross form), each
         into a workspace of the slot's own."""
-        B = int(users.shape[0])
-        if getattr(slot, "ssl_B", -1) != B:
-            slot.ssl_ws = (ops.infonce_workspace(self.n, B, self.d, self.device), ops.infonce_workspace(self.n, B, self.d, self.device))
-            slot.ssl_B = B
-        ops.infonce_plan_raw(users, pos, self.U, self.n, self.d, ops.SSL_RAW, slot.ssl_ws[0], stream=stream)
-        ops.infonce_plan_raw(users, pos, self.U, self.n, self.d, ops.SSL_CROSS, slot.ssl_ws[1], stream=stream)
+        plan_infonce(slot, users, pos, self.U, self.n, self.d, self.device, stream)
 
     def prefetch(self, users, pos, neg):
         """One-batch lookahead of the index-only work of the NEXT step (side stream)."""
@@ -189,24 +196,9 @@ class EgcfAltEngine(EgcfEngine):
             prev = X[l][U:]
         return self.TOT[:U], self.TOT[U:]
 
-    @torch.no_grad()
-    def train_step(self, users, pos, neg, loss_out=None):
-        U = self.U
-        loss = self.loss if loss_out is None else loss_out
-        slot = self.prep.take(users, pos, neg)
-        bitmap = slot.bitmap
+    def _propagate_for_step(self, slot):
+        """The step's forward: the last item product and the item sum at the batch's item rows only."""
         self.propagate(item_rows=slot.items_bitmap)
-        ops.bpr_fused_raw(self.TOT, self.EGO, users, pos, neg, U, self.reg_lambda, self.GT, self.GE, loss=loss[:2],
-                          deterministic=2 | native.IDG_BPR_TOUCHED_PRESET, touched=bitmap, ws=slot.ws)
-        ops.infonce_pair_raw(self.TOT, self.TOT, users, pos, U, self.temperature, g1=self.GT, g2=self.GT, loss=self._ssl[:2],
-                             dedup=False, grad_scale=self.ssl_lambda, accumulate=True, ws=slot.ssl_ws[0], planned=True)
-        ops.infonce_cross_raw(self.TOT, users, pos, U, self.temperature, g=self.GT, loss=self._ssl[2:4],
-                              grad_scale=self.ssl_lambda, ws=slot.ssl_ws[1], planned=True)
-        torch.sum(self._ssl[:3], dim=0, keepdim=True, out=loss[2:3])
-        loss[2:3].mul_(self.ssl_lambda)
-        self._backward(slot, bitmap)
-        self.prep.release(slot)
-        return loss
 
     def _backward(self, slot, bitmap):
         U, K, X = self.U, self.K, self.X

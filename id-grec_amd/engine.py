@@ -9,7 +9,12 @@ operators in ops.py execute (tests compare the two), so models may use either.
 
 Embedding layout: ONE [num_users + num_items, d] panel, users first; the model's two
 nn.Embedding weights are views into it (no torch.cat per step).
+
+For the models whose step is a chain of its own (ngcf.py, gccf.py, bigcf.py, egcf.py) the end of the file holds what they
+share: BatchPrep (the batch's index-only work, one batch ahead), plan_infonce (the InfoNCE id lists as part of it) and
+PanelEngine (the constructor state, the flat buffer of small tensors and the common call sites).
 """
+import ctypes as C
 import os
 
 import torch
@@ -620,7 +625,8 @@ class PropagationEngine:
 class BatchPrep:
     """The index-only work of a batch — the bitmap of its <= 3B panel rows, (optionally) the live work units of that bitmap
     on a graph, the sorted scatter plan of its (row, slot) pairs — on a SIDE stream, one batch ahead of the step that uses
-    it: what PropagationEngine does for the LightGCN family, for engines with their own step (EgcfEngine, NgcfEngine).
+    it: what PropagationEngine does for the LightGCN family, for engines with their own step (EgcfEngine / EgcfAltEngine, and
+    the PanelEngine subclasses NgcfEngine, GccfEngine, BigcfEngine).
     Three slots: the batch being processed, the one prepared ahead, and one whose last step the host has seen complete.
 
         prep.prefetch(users, pos, neg)            # the trainer's lookahead (optional)
@@ -638,7 +644,7 @@ class BatchPrep:
 
     def __init__(self, num_users, n_rows, dim, device, units_graph=None, extra=None):
         """extra(slot, users, pos, neg, raw_stream): more index-only work of the batch, enqueued on the side stream before the
-        slot's `done` event (EgcfEngine: the id lists of its two InfoNCE calls)."""
+        slot's `done` event (EgcfEngine, BigcfEngine: plan_infonce, the id lists of their InfoNCE calls)."""
         self.U, self.n, self.d, self.device, self.graph = int(num_users), int(n_rows), int(dim), device, units_graph
         self.extra = extra
         self._slots = [self._Slot((self.n + 31) // 32, device) for _ in range(3)]  # (three: see PropagationEngine's pacing)
@@ -705,3 +711,107 @@ class BatchPrep:
         slot.free = slot.free_ev
         slot.free.record(torch.cuda.current_stream().cuda_stream)
         self._ends.append(slot.free)
+
+
+def plan_infonce(slot, users, pos, num_users, n_rows, dim, device, stream):
+    """The id-list stages of a step's InfoNCE calls on the raw batch rows — the raw user / item lists (every self-contrast
+    term shares them) into slot.ssl_ws[0], the cross form into slot.ssl_ws[1] — on the side stream `stream`: the body of a
+    BatchPrep `extra` hook.  The two workspaces are the slot's own and are re-made when the batch size changes."""
+    B = int(users.shape[0])
+    if getattr(slot, "ssl_B", -1) != B:
+        slot.ssl_ws = (ops.infonce_workspace(n_rows, B, dim, device), ops.infonce_workspace(n_rows, B, dim, device))
+        slot.ssl_B = B
+    ops.infonce_plan_raw(users, pos, num_users, n_rows, dim, ops.SSL_RAW, slot.ssl_ws[0], stream=stream)
+    ops.infonce_plan_raw(users, pos, num_users, n_rows, dim, ops.SSL_CROSS, slot.ssl_ws[1], stream=stream)
+
+
+class PanelEngine:
+    """What the engines with a step of their own over the packed [n, d] embedding panel and a few small dense tensors share
+    (NgcfEngine, GccfEngine, BigcfEngine): the constructor state, the layout of the small tensors, and the call sites that
+    are the same in every step.  The chain of library calls — forward() / train_step() — is each subclass's own.
+
+    The small tensors live in ONE flat buffer SW, group after group in constructor order (NGCF: K groups of four, GCCF: K of
+    two, BIGCF: two of one), with their gradients SG and both Adam moments SM / SV in the same layout: a backward kernel
+    writes a group's gradients straight into SG at group_offset[g], and one Adam launch updates all of them.  This class is
+    the only place that knows the layout; everything else goes through the views it hands out."""
+
+    def __init__(self, graph, num_users, num_items, params, groups, n_losses, reg_lambda, lr, betas, eps, store_grad):
+        """params: the packed [n, d] embedding panel (users first; updated in place).  groups: tuples of small tensors —
+        copied into SW; small_views() returns the views to re-point the nn.Parameters at."""
+        self.G = graph
+        self.U, self.I = int(num_users), int(num_items)
+        self.n, self.d = int(params.shape[0]), int(params.shape[1])
+        assert self.n == self.U + self.I and params.is_cuda and params.is_contiguous()
+        self.reg_lambda, self.lr, self.betas, self.eps = float(reg_lambda), float(lr), betas, float(eps)
+        self.store_grad = bool(store_grad)
+        self.device = dev = params.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.P = params
+        self.GRAD = torch.empty((self.n, self.d), **f32)
+        self.M, self.V = torch.zeros((self.n, self.d), **f32), torch.zeros((self.n, self.d), **f32)
+        total = sum(t.numel() for g in groups for t in g)
+        self.SW, self.SG = torch.empty(total, **f32), torch.zeros(total, **f32)
+        self.SM, self.SV = torch.zeros(total, **f32), torch.zeros(total, **f32)
+        self.group_offset = []  # of each group's first float in SW / SG / SM / SV
+        self._views, self._gviews = [], []
+        small_moments = []
+        o = 0
+        for g in groups:
+            self.group_offset.append(o)
+            cuts = []  # (first float, floats, shape) of each tensor of the group
+            for t in g:
+                cuts.append((o, t.numel(), tuple(t.shape)))
+                o += t.numel()
+            cut = lambda flat: tuple(flat[a:a + cnt].view(s) for a, cnt, s in cuts)  # noqa: E731
+            self._views.append(cut(self.SW))
+            self._gviews.append(cut(self.SG))
+            small_moments += zip(cut(self.SM), cut(self.SV))
+            for v, src in zip(self._views[-1], g):
+                v.copy_(src)
+        U = self.U
+        self._param_views = [self.P[:U], self.P[U:]] + [v for g in self._views for v in g]
+        self._moment_homes = [(self.M[:U], self.V[:U]), (self.M[U:], self.V[U:])] + small_moments
+        self.prep = None  # the subclass's BatchPrep
+        self.loss = torch.zeros(n_losses, **f32)
+        self.step_count = 0
+
+    def small_views(self):
+        return self._views
+
+    def small_grads(self):
+        return self._gviews
+
+    def param_views(self):
+        """Where the parameters live: the user rows and the item rows of P, then the small tensors in constructor order."""
+        return self._param_views
+
+    def moment_homes(self):
+        """(exp_avg, exp_avg_sq) views of M / V and SM / SV in param_views()'s order — user rows, item rows, then the small
+        tensors in constructor order: what modeling.adopt_adam_state makes an optimizer's state entries be."""
+        return self._moment_homes
+
+    @staticmethod
+    def _p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
+    def _bpr(self, final, ld, users, pos, neg, reg_mode, loss, g_final, slot):
+        """BPR on the rows of `final` (leading dimension ld) + the regulariser on P's rows (reg_mode 0: the item rows of the
+        batch, 1: its user rows too): loss[0:2], d loss / d final STORED at the batch's rows of g_final, the regulariser's
+        rows in GE — by the slot's scatter plan, the batch's rows taken from its bitmap."""
+        p_ = self._p
+        native.check(native.lib.idg_bpr_fused_ex_f32(
+            p_(final), ld, p_(self.P), self.d, self.U, self.n, p_(users), p_(pos), p_(neg), int(users.shape[0]), self.reg_lambda,
+            reg_mode, p_(loss), p_(g_final), p_(self.GE), native.IDG_BPR_PLANNED | native.IDG_BPR_TOUCHED_PRESET, p_(slot.bitmap),
+            p_(slot.ws), ops._stream()), "idg_bpr_fused_ex_f32")
+
+    def _adam(self):
+        """The Adam arguments of the product whose epilogue updates the embedding panel (at the current step_count)."""
+        return (self.P, self.M, self.V, self.lr, self.step_count, self.betas[0], self.betas[1], self.eps)
+
+    def _adam_small(self):
+        """The one Adam launch for every small tensor."""
+        ops.adam_step_raw(self.SW, self.SG, self.SM, self.SV, self.lr, self.step_count, self.betas[0], self.betas[1], self.eps)
+
+    def prefetch(self, users, pos, neg):
+        """One-batch lookahead of the index-only work of the NEXT step (side stream)."""
+        self.prep.prefetch(users, pos, neg)

@@ -25,6 +25,111 @@ def adam_group_over(optimizer, params):
     return group
 
 
+def adopt_adam_state(optimizer, homes):
+    """Make the Adam moments of `optimizer` live where a fused step updates them.  homes: [(parameter, exp_avg home,
+    exp_avg_sq home), ...].  A state entry that is empty, or whose exp_avg is not already the home, is re-homed: what the
+    optimizer has accumulated is copied in, and the entry then IS the home — the optimizer's state stays the single source of
+    truth, whichever way the next step is taken.  Returns the parameters' common step count, or None (the re-homing done all
+    the same) when their counters disagree."""
+    steps = set()
+    for prm, m, v in homes:
+        st = optimizer.state[prm]
+        if not st or st["exp_avg"].data_ptr() != m.data_ptr():
+            if st:  # the optimizer has already stepped the other way: keep what it accumulated
+                m.copy_(st["exp_avg"])
+                v.copy_(st["exp_avg_sq"])
+            st.setdefault("step", 0)
+            st["exp_avg"], st["exp_avg_sq"] = m, v
+        steps.add(int(st["step"]))
+    return steps.pop() if len(steps) == 1 else None
+
+
+class EngineStep:
+    """The trainer protocol (fused_train_step, fused_loss_and_grad, prefetch_batch) of a model whose fused step is an engine
+    of its own (NGCF, GCCF, BIGCF: a PanelEngine; EGCF: EgcfEngine / EgcfAltEngine) — a mixin, listed before the nn.Module
+    base.  The model supplies fused_step_available() and three things:
+        _fused_engine()   its engine getter; after (re)building an engine it calls _adopt_engine(eng)
+        _engine_params()  its parameters in the order of the engine's param_views() / moment_homes()
+        _step_kwargs()    further keyword arguments of the engine's train_step (default: none)"""
+    _fused_params = None  # _engine_params(), listed once
+    _fused_homes = None   # [(parameter, exp_avg home, exp_avg_sq home)] in the current engine
+
+    def _fused_engine(self):
+        raise NotImplementedError
+
+    def _engine_params(self):
+        raise NotImplementedError
+
+    def _step_kwargs(self):
+        return {}
+
+    def _step_params(self):
+        if self._fused_params is None:
+            self._fused_params = self._engine_params()
+        return self._fused_params
+
+    def _engine_is_current(self, eng):
+        """Whether the parameters still live in `eng`'s storage: not before the first engine, nor after .to() or a re-pack
+        has re-created the tensors (the first and the last parameter tell)."""
+        if eng is None:
+            return False
+        params, views = self._step_params(), eng.param_views()
+        return params[0].data_ptr() == views[0].data_ptr() and params[-1].data_ptr() == views[-1].data_ptr()
+
+    def _adopt_engine(self, eng):
+        """After `eng` was (re)built: the parameters now live in ITS storage — re-point every nn.Parameter at the engine's
+        view — and pair them, once, with the homes of their Adam moments."""
+        params = self._step_params()
+        for prm, view in zip(params, eng.param_views()):
+            prm.data = view
+        self._fused_homes = [(prm, m, v) for prm, (m, v) in zip(params, eng.moment_homes())]
+        return eng
+
+    def _engine_adam(self, optimizer):
+        """The hand-off of a fused step to `optimizer`: (param group, common step count), or None — nothing stepped — unless
+        it is an idgrec_amd.ops.Adam over exactly _engine_params(), the fused step is available, and the step counters
+        agree.  The moments are re-homed into the engine's buffers (adopt_adam_state)."""
+        group = adam_group_over(optimizer, self._step_params())
+        if group is None or not self.fused_step_available():
+            return None
+        self._fused_engine()
+        step = adopt_adam_state(optimizer, self._fused_homes)
+        return None if step is None else (group, step)
+
+    def fused_train_step(self, users, pos, neg, loss_out, optimizer):
+        """forward + backward + every Adam update as ONE chain of kernels, in the state of `optimizer` as _engine_adam hands
+        it over; False (nothing done) when it does not.  Its state stays the single source of truth."""
+        adam = self._engine_adam(optimizer)
+        if adam is None:
+            return False
+        group, step = adam
+        eng = self._fused_engine()
+        eng.lr, eng.betas, eng.eps = float(group["lr"]), tuple(group["betas"]), float(group["eps"])
+        eng.step_count = step
+        self._eval_cache = None
+        eng.train_step(users, pos, neg, loss_out, **self._step_kwargs())
+        for prm in self._fused_params:
+            optimizer.state[prm]["step"] = eng.step_count
+        return True
+
+    def fused_loss_and_grad(self, users, pos, neg, loss_out=None):
+        """The trainer's fallback when the optimizer is not ours: the differentiable operators under autograd."""
+        self._eval_cache = None
+        ll = self.forward(users, pos, neg)
+        self.zero_grad()
+        sum(ll).backward()
+        out = torch.stack([x.detach() for x in ll])
+        if loss_out is not None:
+            loss_out.copy_(out)
+        return out
+
+    def prefetch_batch(self, users, pos, neg):
+        """The trainer's one-batch lookahead: the next batch's index-only work (bitmaps, scatter plan, id lists) on the
+        engine's side stream."""
+        if self.fused_step_available():
+            self._fused_engine().prefetch(users, pos, neg)
+
+
 class _PackedPanel(torch.autograd.Function):
     """(user_weight, item_weight) -> the [n, d] panel they both live in, without copying."""
 
@@ -156,18 +261,13 @@ class PackedRecommender(nn.Module):
             self._pack()
         U = self.dataset.num_users
         st_u, st_i = optimizer.state[uw], optimizer.state[iw]
-        packed = getattr(self, "_packed_moments", None)
+        packed, homes = getattr(self, "_packed_moments", (None, None))
+        # (an optimizer whose state is not in the panels yet gets FRESH ones: moments another optimizer left are not its own)
         if (packed is None or packed[0].device != self._storage.device or not st_u or not st_i
-                or st_u["exp_avg"].data_ptr() != packed[0].data_ptr() or st_i["exp_avg_sq"].data_ptr() != packed[1][U:].data_ptr()):
+                or st_u["exp_avg"].data_ptr() != homes[0][1].data_ptr() or st_i["exp_avg_sq"].data_ptr() != homes[1][2].data_ptr()):
             m, v = torch.zeros_like(self._storage), torch.zeros_like(self._storage)
-            for st, sl in ((st_u, slice(0, U)), (st_i, slice(U, None))):
-                if st:  # the optimizer has already stepped the other way: keep what it accumulated
-                    m[sl].copy_(st["exp_avg"])
-                    v[sl].copy_(st["exp_avg_sq"])
-                st.setdefault("step", 0)
-                st["exp_avg"], st["exp_avg_sq"] = m[sl], v[sl]
-            packed = self._packed_moments = (m, v)
-        if st_u["step"] != st_i["step"]:
+            packed, homes = self._packed_moments = (m, v), [(uw, m[:U], v[:U]), (iw, m[U:], v[U:])]
+        if adopt_adam_state(optimizer, homes) is None:
             return None
         return group, st_u, st_i, packed
 

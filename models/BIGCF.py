@@ -20,10 +20,10 @@ import utility.utility_function.losses as losses
 import utility.utility_train.trainer as trainer
 from idgrec_amd import ops
 from idgrec_amd.bigcf import BigcfEngine
-from idgrec_amd.modeling import PackedRecommender, adam_group_over
+from idgrec_amd.modeling import EngineStep, PackedRecommender
 
 
-class BIGCF(PackedRecommender):
+class BIGCF(EngineStep, PackedRecommender):
     #: trains through a fused chain of library calls (idgrec_amd/bigcf.py) at (embedding_size, intent_size) = (64, 128);
     #: otherwise through the differentiable operators below
     supports_fused_step = True
@@ -69,62 +69,20 @@ class BIGCF(PackedRecommender):
         if not self._is_packed():
             self._pack()
         eng = getattr(self, "_bigcf_engine", None)
-        wu, wi = self.user_intent.weight, self.item_intent.weight
-        if eng is None or eng.P.data_ptr() != self._storage.data_ptr() or wu.data_ptr() != eng.intent_views()[0].data_ptr():
-            eng = self._bigcf_engine = BigcfEngine(self.Graph, self.dataset.num_users, self.dataset.num_items, self._storage,
-                                                   (wu.data, wi.data), self.n_layers, reg_lambda=self.reg_lambda,
-                                                   ssl_lambda=self.ssl_lambda, temperature=self.ssl_temperature)
-            wu.data, wi.data = eng.intent_views()
+        if not self._engine_is_current(eng):
+            eng = self._bigcf_engine = self._adopt_engine(BigcfEngine(
+                self.Graph, self.dataset.num_users, self.dataset.num_items, self._storage,
+                (self.user_intent.weight.data, self.item_intent.weight.data), self.n_layers, reg_lambda=self.reg_lambda,
+                ssl_lambda=self.ssl_lambda, temperature=self.ssl_temperature))
         return eng
 
-    def prefetch_batch(self, users, pos, neg):
-        """The trainer's one-batch lookahead: the next batch's bitmaps, scatter plan and InfoNCE id lists on the side stream."""
-        if self.fused_step_available():
-            self.bigcf_engine().prefetch(users, pos, neg)
+    _fused_engine = bigcf_engine
 
-    def fused_train_step(self, users, pos, neg, loss_out, optimizer):
-        """forward + backward + every Adam update as ONE chain of kernels; False (nothing done) unless `optimizer` is an
-        idgrec_amd.ops.Adam over exactly this model's parameters.  Its state stays the single source of truth."""
-        group = adam_group_over(optimizer, list(self.parameters()))
-        if group is None or not self.fused_step_available():
-            return False
-        eng = self.bigcf_engine()
-        U, per, shape = self.dataset.num_users, eng._per, (eng.d, eng.k)
-        # (parameter, first-moment view, second-moment view): the two tables in the packed panels, the intent matrices in the
-        # flat buffers
-        homes = [(self.user_embedding.weight, eng.M[:U], eng.V[:U]), (self.item_embedding.weight, eng.M[U:], eng.V[U:]),
-                 (self.user_intent.weight, eng.SM[:per].view(shape), eng.SV[:per].view(shape)),
-                 (self.item_intent.weight, eng.SM[per:].view(shape), eng.SV[per:].view(shape))]
-        steps = set()
-        for prm, m, v in homes:
-            st = optimizer.state[prm]
-            if not st or st["exp_avg"].data_ptr() != m.data_ptr():
-                if st:  # the optimizer has already stepped the other way: keep what it accumulated
-                    m.copy_(st["exp_avg"])
-                    v.copy_(st["exp_avg_sq"])
-                st.setdefault("step", 0)
-                st["exp_avg"], st["exp_avg_sq"] = m, v
-            steps.add(int(st["step"]))
-        if len(steps) != 1:
-            return False
-        eng.lr, eng.betas, eng.eps = float(group["lr"]), tuple(group["betas"]), float(group["eps"])
-        eng.step_count = steps.pop()
-        self._eval_cache = None
-        eng.train_step(users, pos, neg, loss_out, noise=self._noise())
-        for prm, _, _ in homes:
-            optimizer.state[prm]["step"] = eng.step_count
-        return True
+    def _engine_params(self):
+        return [self.user_embedding.weight, self.item_embedding.weight, self.user_intent.weight, self.item_intent.weight]
 
-    def fused_loss_and_grad(self, users, pos, neg, loss_out=None):
-        """The trainer's fallback when the optimizer is not ours: the differentiable operators under autograd."""
-        self._eval_cache = None
-        ll = self.forward(users, pos, neg)
-        self.zero_grad()
-        sum(ll).backward()
-        out = torch.stack([x.detach() for x in ll])
-        if loss_out is not None:
-            loss_out.copy_(out)
-        return out
+    def _step_kwargs(self):
+        return dict(noise=self._noise())
 
     # ------------------------------------------------------------------ differentiable path
     def _noise(self):

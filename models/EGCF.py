@@ -20,10 +20,10 @@ import utility.utility_function.tools as tools
 import utility.utility_train.trainer as trainer
 from idgrec_amd import ops
 from idgrec_amd.egcf import EgcfAltEngine, EgcfEngine
-from idgrec_amd.modeling import adam_group_over
+from idgrec_amd.modeling import EngineStep
 
 
-class EGCF(nn.Module):
+class EGCF(EngineStep, nn.Module):
     #: both encoders train through fused, autograd-free chains of library calls (idgrec_amd/egcf.py: EgcfEngine for
     #: `parallel`, EgcfAltEngine for `alternating`); the differentiable operators below serve foreign optimizers
     supports_fused_step = True
@@ -66,55 +66,21 @@ class EGCF(nn.Module):
     def engine(self):
         """The fused engine; the item table lives in ITS storage (nn.Embedding.weight is re-pointed at it), so that the
         regulariser's [n, d] view of the parameters and the table are one buffer."""
-        w = self.item_embedding.weight
-        if self._engine is None or w.data_ptr() != self._engine.item_table().data_ptr():
+        if not self._engine_is_current(self._engine):
+            w = self.item_embedding.weight
             if self.aggregate_mode == 'parallel':
-                self._engine = EgcfEngine(self.Graph, self.user_Graph, self.dataset.num_users, self.dataset.num_items,
-                                          int(w.shape[1]), self.n_layers, w.data, self.reg_lambda, self.ssl_lambda,
-                                          self.temperature)
+                eng = EgcfEngine(self.Graph, self.user_Graph, self.dataset.num_users, self.dataset.num_items,
+                                 int(w.shape[1]), self.n_layers, w.data, self.reg_lambda, self.ssl_lambda, self.temperature)
             else:
-                self._engine = EgcfAltEngine(self.user_Graph, self.dataset.num_users, self.dataset.num_items, int(w.shape[1]),
-                                             self.n_layers, w.data, self.reg_lambda, self.ssl_lambda, self.temperature)
-            w.data = self._engine.item_table()
+                eng = EgcfAltEngine(self.user_Graph, self.dataset.num_users, self.dataset.num_items, int(w.shape[1]),
+                                    self.n_layers, w.data, self.reg_lambda, self.ssl_lambda, self.temperature)
+            self._engine = self._adopt_engine(eng)
         return self._engine
 
-    def prefetch_batch(self, users, pos, neg):
-        """The trainer's one-batch lookahead: the next batch's bitmap / live units / scatter plan on the side stream."""
-        if self.fused_step_available():
-            self.engine().prefetch(users, pos, neg)
+    _fused_engine = engine
 
-    def fused_train_step(self, users, pos, neg, loss_out, optimizer):
-        """forward + backward + Adam as ONE chain of kernels; False (nothing done) unless `optimizer` is an
-        idgrec_amd.ops.Adam over exactly the item table.  The optimizer's state stays the single source of truth."""
-        w = self.item_embedding.weight
-        group = adam_group_over(optimizer, [w])
-        if group is None:
-            return False
-        eng = self.engine()
-        st = optimizer.state[w]
-        if not st or st["exp_avg"].data_ptr() != eng.M.data_ptr():
-            if st:  # the optimizer has already stepped the other way: keep what it accumulated
-                eng.M.copy_(st["exp_avg"])
-                eng.V.copy_(st["exp_avg_sq"])
-            st.setdefault("step", 0)
-            st["exp_avg"], st["exp_avg_sq"] = eng.M, eng.V
-        eng.lr, eng.betas, eng.eps = float(group["lr"]), tuple(group["betas"]), float(group["eps"])
-        eng.step_count = int(st["step"])
-        self._eval_cache = None
-        eng.train_step(users, pos, neg, loss_out)
-        st["step"] = eng.step_count
-        return True
-
-    def fused_loss_and_grad(self, users, pos, neg, loss_out=None):
-        """The trainer's fallback when the optimizer is not ours: the differentiable operators under autograd."""
-        self._eval_cache = None
-        ll = self.forward(users, pos, neg)
-        self.zero_grad()
-        sum(ll).backward()
-        out = torch.stack([x.detach() for x in ll])
-        if loss_out is not None:
-            loss_out.copy_(out)
-        return out
+    def _engine_params(self):
+        return [self.item_embedding.weight]
 
     def alternating_aggregate(self):
         item = self.item_embedding.weight
