@@ -1346,6 +1346,96 @@ def gccf_layer(side, W, b, p, stream=None):
     return ngcf_layer_tail(tall_linear(side, W), None, b, torch.zeros_like(b), 1.0, float(p), stream)[0]
 
 
+# ----------------------------------------------------------------------------------- GCMC's two-transform layer
+GCMC_SLOPE = 0.2  # nn.LeakyReLU(negative_slope=0.2) (models/GCMC.py:80)
+_gcmc_ws = {}
+
+
+def gcmc_layer_fwd_raw(side, Wg, bg, Wm, bm, p, seed, stream_id, T, N, ldn=None, slot=0, slope=GCMC_SLOPE):
+    """idg_gcmc_layer_fwd_f32: T = keep * (leaky_relu(side . Wg + bg) . Wm + bm) contiguous [n, 64]; N = T / max(|T|, 1e-12)
+    written `slot` floats into each row of N with leading dimension ldn (default: N's own width)."""
+    _require_device(side, Wg, bg, Wm, bm, T, N)
+    n, d = side.shape
+    check(lib.idg_gcmc_layer_fwd_f32(_ptr(side), _ptr(Wg), _ptr(bg), _ptr(Wm), _ptr(bm), n, d, float(slope), float(p),
+                                     C.c_uint64(seed), C.c_uint64(stream_id), _ptr(T), N.data_ptr() + 4 * int(slot),
+                                     int(N.shape[1] if ldn is None else ldn), _stream()), "idg_gcmc_layer_fwd_f32")
+    return T, N
+
+
+def gcmc_layer_bwd_raw(T, gE, gN, ldgn, gn_rows, side, Wg, bg, Wm, p, seed, stream_id, g_side, w_grads, gn_slot=0,
+                       slope=GCMC_SLOPE):
+    """idg_gcmc_layer_bwd_f32: gM = keep * (gE + J_normalize(T)^T gN at the rows of the bitmap gn_rows), then the layer's
+    backward with H and A recomputed from side; g_side [n, 64]; w_grads = [gWg | gbg | gWm | gbm].  gN is read `gn_slot`
+    floats into each row, leading dimension ldgn."""
+    _require_device(T, gE, gN, gn_rows, side, Wg, bg, Wm, g_side, w_grads)
+    n, d = side.shape
+    ws = _gcmc_ws.get((d, side.device))
+    if ws is None:
+        ws = _gcmc_ws[(d, side.device)] = torch.empty(max(int(lib.idg_gcmc_layer_bwd_workspace_bytes(d)), 16), dtype=torch.uint8,
+                                                      device=side.device)
+    check(lib.idg_gcmc_layer_bwd_f32(_ptr(T), _ptr(gE), None if gN is None else gN.data_ptr() + 4 * int(gn_slot), int(ldgn),
+                                     _ptr(gn_rows), _ptr(side), _ptr(Wg), _ptr(bg), _ptr(Wm), n, d, float(slope), float(p),
+                                     C.c_uint64(seed), C.c_uint64(stream_id), _ptr(g_side), _ptr(w_grads), _ptr(ws), _stream()),
+          "idg_gcmc_layer_bwd_f32")
+    return g_side, w_grads
+
+
+class _GcmcLayer(torch.autograd.Function):
+    """(T, N) of one GCMC layer at d = 64 in one kernel per direction (csrc/idg_gcmc.hip).  The backward reads T and side:
+    H and A are recomputed, the mask regenerated from (seed, stream id)."""
+
+    @staticmethod
+    def forward(ctx, side, Wg, bg, Wm, bm, p, stream):
+        seed, sid = stream
+        T, N = torch.empty_like(side), torch.empty_like(side)
+        gcmc_layer_fwd_raw(side, Wg, bg.reshape(-1), Wm, bm.reshape(-1), p, seed, sid, T, N)
+        ctx.save_for_backward(side, Wg, bg, Wm, T)
+        ctx.args = (float(p), seed, sid, bg.shape, bm.shape)
+        return T, N
+
+    @staticmethod
+    def backward(ctx, gT, gN):
+        side, Wg, bg, Wm, T = ctx.saved_tensors
+        p, seed, sid, bg_shape, bm_shape = ctx.args
+        d = Wg.shape[0]
+        g_side = torch.empty_like(side)
+        w_grads = torch.empty(2 * (d * d + d), dtype=torch.float32, device=side.device)
+        gcmc_layer_bwd_raw(T, None if gT is None else _f32c(gT, "gT"), None if gN is None else _f32c(gN, "gN"), d, None, side, Wg,
+                           bg.reshape(-1), Wm, p, seed, sid, g_side, w_grads)
+        h = d * d + d
+        return (g_side, w_grads[:d * d].view(d, d), w_grads[d * d:h].view(bg_shape), w_grads[h:h + d * d].view(d, d),
+                w_grads[h + d * d:].view(bm_shape), None, None)
+
+
+def gcmc_layer(side, Wg, bg, Wm, bm, p, stream=None):
+    """One GCMC layer after the sparse product (models/GCMC.py:77-88): M = leaky_relu(side @ Wg + bg, 0.2) @ Wm + bm,
+    T = nn.Dropout(p)(M) (the next layer's input), N = normalize(T) (what is concatenated).  Returns (T, N).
+    side [n, d1], Wg [d1, d2], Wm [d2, d3], biases [1, .] or [.].  Both matrices [64, 64]: idg_gcmc_layer_fwd_f32 /
+    idg_gcmc_layer_bwd_f32; any other width, and rectangular layers: tall_linear and ngcf_layer_tail twice — slope 0.2 without
+    a mask for the activation, then slope 1 with the mask, whose outputs are exactly (dropout(M), its normalised copy).
+    stream: (seed, stream id) of the dropout mask; default: the next one of the device seed's sequence."""
+    for t, name in ((side, "side"), (Wg, "Wg"), (bg, "bg"), (Wm, "Wm"), (bm, "bm")):
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be float32 (got %s)" % (name, t.dtype))
+    if side.dim() != 2 or Wg.dim() != 2 or Wm.dim() != 2:
+        raise ValueError("gcmc_layer: side must be [n, d], Wg [d, d2] and Wm [d2, d3], got %s, %s and %s"
+                         % (tuple(side.shape), tuple(Wg.shape), tuple(Wm.shape)))
+    if side.shape[1] != Wg.shape[0] or bg.numel() != Wg.shape[1] or Wm.shape[0] != Wg.shape[1] or bm.numel() != Wm.shape[1]:
+        raise ValueError("gcmc_layer: side %s, Wg %s, bg %s, Wm %s and bm %s do not fit (side [n, d], Wg [d, d2], bg [1, d2], "
+                         "Wm [d2, d3], bm [1, d3])" % tuple(tuple(t.shape) for t in (side, Wg, bg, Wm, bm)))
+    if side.shape[0] == 0:
+        raise ValueError("gcmc_layer: side has 0 rows")
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError("gcmc_layer: drop probability p = %g outside [0, 1)" % float(p))
+    _require_device(side, Wg, bg, Wm, bm)
+    stream = _next_noise_stream() if stream is None else stream
+    if tuple(Wg.shape) == (64, 64) and tuple(Wm.shape) == (64, 64):
+        return _GcmcLayer.apply(_f32c(side, "side"), _f32c(Wg, "Wg"), _f32c(bg, "bg"), _f32c(Wm, "Wm"), _f32c(bm, "bm"), float(p),
+                                stream)
+    A = ngcf_layer_tail(tall_linear(side, Wg), None, bg, torch.zeros_like(bg), GCMC_SLOPE, 0.0, stream)[0]
+    return ngcf_layer_tail(tall_linear(A, Wm), None, bm, torch.zeros_like(bm), 1.0, float(p), stream)
+
+
 # ----------------------------------------------------------------------------------- BIGCF's intent layer
 _intent_ws = {}
 

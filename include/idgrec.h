@@ -582,6 +582,31 @@ size_t idg_gccf_layer_bwd_workspace_bytes(int64_t d);
 int idg_gccf_layer_bwd_f32(const float* gE, const float* gN, int64_t ldgn, const uint32_t* gn_rows, const float* side,
                            const float* W, int64_t n, int64_t d, float p, uint64_t seed, uint64_t stream_id, float* g_side,
                            float* w_grads, void* ws, void* stream);
+/* One GCMC layer (models/GCMC.py:73-90) as ONE kernel per direction, d = 64 (csrc/idg_gcmc.hip): two CHAINED products with
+ * the activation between them, the mask, and a row normalisation behind the mask.
+ *   forward : H = side . Wg + bg;  A = leaky_relu(H);  M = A . Wm + bm;  T = keep * M, written contiguous [n, 64] (the next
+ *             layer's product input and the only activation the backward reads);  N = T / max(|T|_2, 1e-12), written with
+ *             leading dimension ldn (layer l's slot of the concatenated final rows).  H and A are not stored; nothing is
+ *             written outside rows 0 .. n-1 of T and of the slot;
+ *   backward: N and its denominator rebuilt from T;  gM = keep * ((gE or 0) + J_normalize(T)^T gN at the rows flagged in
+ *             gn_rows) — gn_rows = NULL: every row; what gN holds off the flagged rows is never read; a row below the clamp
+ *             has the Jacobian I / 1e-12 (idg_ngcf_tail_bwd_ex_f32's convention); at least one of gE, gN must be given.
+ *             H is recomputed from side with the forward's operand order (the forward's bits), the slope applies where
+ *             H <= 0.  g_side = ((gM . Wm^T) o leaky_relu'(H)) . Wg^T [n, 64];
+ *             w_grads = [gWg (64 x 64) = side^T . gH | gbg (64) | gWm (64 x 64) = A^T . gM | gbm (64)].
+ * The sums over rows run in a fixed order (slices of rows on persistent workgroups, added in slice order): two runs give
+ * the same bits.  Any other d, NULL or misaligned pointers (panels and, in the backward, Wg and Wm: 16 bytes), n <= 0, a
+ * leading dimension below d or not a multiple of 4, p outside [0, 1) and outputs that overlap inputs or each other:
+ * IDG_E_INVALID before any device work.  ws: as many bytes as idg_gcmc_layer_bwd_workspace_bytes returns for d (0 for a
+ * width that is not built). */
+int idg_gcmc_layer_fwd_f32(const float* side, const float* Wg, const float* bg, const float* Wm, const float* bm, int64_t n,
+                           int64_t d, float negative_slope, float p, uint64_t seed, uint64_t stream_id, float* T, float* N,
+                           int64_t ldn, void* stream);
+size_t idg_gcmc_layer_bwd_workspace_bytes(int64_t d);
+int idg_gcmc_layer_bwd_f32(const float* T, const float* gE, const float* gN, int64_t ldgn, const uint32_t* gn_rows,
+                           const float* side, const float* Wg, const float* bg, const float* Wm, int64_t n, int64_t d,
+                           float negative_slope, float p, uint64_t seed, uint64_t stream_id, float* g_side, float* w_grads,
+                           void* ws, void* stream);
 /* Glue of that step.  idg_copy_cols_f32: dst[r, 0:d] = src[r, 0:d] with leading dimensions ldd / lds.  idg_rows_add2_f32:
  * dst[r] += a[r] (+ b[r]) at the rows flagged in `rows`.  idg_colsum_f32: out[f] (+)= sum over the n rows of X[r, f] — the
  * gradient of a bias row broadcast over n rows (the differentiable layer tail's backward; the fused step gets it from
