@@ -156,6 +156,13 @@ PROTOTYPES = {
     "idg_gcmc_layer_bwd_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "idg_gcmc_layer_bwd_f32": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float,
                                          C.c_float, C.c_uint64, C.c_uint64, c_vp, c_vp, c_vp, c_vp]),
+    "idg_group_assign_f32": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_float,
+                                       C.c_uint64, C.c_uint64, C.c_uint64, c_vp, c_vp, c_vp]),
+    "idg_grouped_spmm_chunk": (C.c_int64, []),
+    "idg_grouped_spmm_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "idg_grouped_spmm_f32": (C.c_int, [C.c_int64, C.c_int64, c_vp, c_vp, c_vp, C.c_int64, C.c_int, c_vp, c_vp, C.c_int64, c_vp, c_vp,
+                                       c_vp, c_vp, C.c_int64, c_vp, c_vp, c_vp, c_vp, C.c_int64, C.c_int64, c_vp, c_vp]),
+    "idg_group_grad_f32": (C.c_int, [c_vp, C.c_float, c_vp, C.c_float, c_vp, c_vp, C.c_int64, C.c_int64, c_vp, c_vp]),
     "idg_intent_noise_f32": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, c_vp, c_vp]),
     "idg_intent_fwd_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int64, C.c_int64, c_vp, c_vp, C.c_uint64,
                                      C.c_uint64, c_vp, C.c_int64, c_vp, C.c_int64, c_vp, c_vp]),

@@ -1436,6 +1436,253 @@ def gcmc_layer(side, Wg, bg, Wm, bm, p, stream=None):
     return ngcf_layer_tail(tall_linear(A, Wm), None, bm, torch.zeros_like(bm), 1.0, float(p), stream)
 
 
+# ----------------------------------------------------------------------------------- IMP-GCN's groups
+IMPGCN_SLOPE = 0.01  # nn.LeakyReLU() (models/IMPGCN.py:35)
+IMPGCN_DROP = 0.4    # nn.Dropout(p=0.4), hard-coded (models/IMPGCN.py:36)
+GROUP_MAX = 8        # a membership is one byte
+
+
+class GroupCsr:
+    """A plain device CSR (indptr int64, indices int32 ascending per row, values fp32; square) for idg_grouped_spmm_f32, with
+    the schedule of its rows longer than one chunk (built once, on the host) and, optionally, the ops.Graph handle of the
+    same matrix, through which widths other than 64 are composed.  The host arrays are checked here — every index inside
+    0 .. n - 1, indptr monotone from 0 to nnz: the kernel trusts them."""
+
+    def __init__(self, indptr, indices, values, n, device, graph=None, schedule=True):
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        n = int(n)
+        if indptr.shape != (n + 1,) or indices.shape != values.shape or indices.ndim != 1:
+            raise ValueError("GroupCsr: indptr must be [n + 1] and indices / values [nnz] (got %s, %s, %s for n = %d)"
+                             % (indptr.shape, indices.shape, values.shape, n))
+        lens = np.diff(indptr)
+        if n < 1 or indptr[0] != 0 or indptr[-1] != indices.shape[0] or (lens < 0).any():
+            raise ValueError("GroupCsr: indptr must rise from 0 to nnz = %d over n >= 1 rows" % indices.shape[0])
+        if indices.shape[0] and (indices.min() < 0 or indices.max() >= n):
+            raise ValueError("GroupCsr: a column index lies outside 0 .. %d (the matrix is square)" % (n - 1))
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("idgrec_amd operators run on MI355X only: GroupCsr needs a cuda(HIP) device, got %s" % dev)
+        self.n, self.nnz, self.device, self.graph = n, int(indices.shape[0]), dev, graph
+        self.indptr = torch.from_numpy(indptr).to(dev)
+        self.indices = torch.from_numpy(indices).to(dev)
+        self.values = torch.from_numpy(values).to(dev)
+        chunk = int(lib.idg_grouped_spmm_chunk())
+        long_rows = np.nonzero(lens > chunk)[0].astype(np.int32) if schedule else np.zeros(0, dtype=np.int32)
+        chunk0 = np.concatenate([[0], np.cumsum((lens[long_rows] + chunk - 1) // chunk)]).astype(np.int32)
+        self.n_long, self.n_chunks = int(long_rows.shape[0]), int(chunk0[-1])
+        self.long_rows = torch.from_numpy(long_rows).to(dev) if self.n_long else None
+        self.long_chunk0 = torch.from_numpy(chunk0).to(dev) if self.n_long else None
+        self._ws = {}
+
+    @classmethod
+    def from_scipy(cls, mat, device, graph=None, schedule=True):
+        m = mat.tocsr().astype(np.float32)
+        m.sort_indices()
+        if m.shape[0] != m.shape[1]:
+            raise ValueError("GroupCsr: the matrix must be square, got %s" % (m.shape,))
+        return cls(m.indptr, m.indices, m.data, m.shape[0], device, graph=graph, schedule=schedule)
+
+    def workspace(self, G):
+        if not self.n_long:
+            return None
+        ws = self._ws.get(G)
+        if ws is None:
+            ws = self._ws[G] = torch.empty(int(lib.idg_grouped_spmm_workspace_bytes(self.n_chunks, G)), dtype=torch.uint8, device=self.device)
+        return ws
+
+
+def _check_groups(who, G):
+    if int(G) != G or not 1 <= int(G) <= GROUP_MAX:
+        raise ValueError("%s: G = %s outside 1 .. %d (a membership is one byte)" % (who, G, GROUP_MAX))
+    return int(G)
+
+
+def _check_member(who, member, n):
+    if member.dtype != torch.uint8:
+        raise TypeError("%s: member must be uint8, one byte per node (got %s)" % (who, member.dtype))
+    if tuple(member.shape) != (n,) or not member.is_contiguous():
+        raise ValueError("%s: member must be a contiguous [%d] vector, got %s" % (who, n, tuple(member.shape)))
+
+
+def group_assign_raw(ego, side, W_fc, b_fc, W_grp, b_grp, num_users, p, seed, stream_fc, stream_grp, member=None, scores_out=None,
+                     slope=IMPGCN_SLOPE):
+    """idg_group_assign_f32: member[r] = the bitmask of the groups whose masked score is the row's maximum (user rows), every
+    group (rows >= num_users).  ego, side [n, 64]; W_fc [64, 64], W_grp [G, 64] in nn.Linear's [out, in] layout.  The two
+    masks are the published function of (seed, stream_fc, row, feature) and (seed, stream_grp, row, g).  scores_out [n, G]
+    (optional) receives the masked scores as compared.  Returns member (uint8 [n])."""
+    who = "group_assign_raw"
+    for t, name in ((ego, "ego"), (side, "side"), (W_fc, "W_fc"), (b_fc, "b_fc"), (W_grp, "W_grp"), (b_grp, "b_grp"), (scores_out, "scores_out")):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("%s: %s must be float32 (got %s)" % (who, name, t.dtype))
+    if ego.dim() != 2 or ego.shape[1] != 64 or ego.shape != side.shape or ego.shape[0] == 0:
+        raise ValueError("%s: ego and side must both be [n >= 1, 64], got %s and %s" % (who, tuple(ego.shape), tuple(side.shape)))
+    n = int(ego.shape[0])
+    if tuple(W_fc.shape) != (64, 64) or b_fc.numel() != 64 or W_grp.dim() != 2 or W_grp.shape[1] != 64 or b_grp.numel() != W_grp.shape[0]:
+        raise ValueError("%s: W_fc %s, b_fc %s, W_grp %s and b_grp %s do not fit ([64, 64], [64], [G, 64], [G])"
+                         % (who, tuple(W_fc.shape), tuple(b_fc.shape), tuple(W_grp.shape), tuple(b_grp.shape)))
+    G = _check_groups(who, W_grp.shape[0])
+    if not 0 <= int(num_users) <= n:
+        raise ValueError("%s: num_users = %d outside 0 .. n = %d" % (who, num_users, n))
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError("%s: drop probability p = %g outside [0, 1)" % (who, float(p)))
+    if member is None:
+        member = torch.empty(n, dtype=torch.uint8, device=ego.device)
+    _check_member(who, member, n)
+    if scores_out is not None and (tuple(scores_out.shape) != (n, G) or not scores_out.is_contiguous()):
+        raise ValueError("%s: scores_out must be a contiguous [%d, %d] panel, got %s" % (who, n, G, tuple(scores_out.shape)))
+    _require_device(ego, side, W_fc, b_fc, W_grp, b_grp, member, scores_out)
+    check(lib.idg_group_assign_f32(_ptr(_f32c(ego, "ego")), _ptr(_f32c(side, "side")), _ptr(_f32c(W_fc, "W_fc")), _ptr(_f32c(b_fc, "b_fc")),
+                                   _ptr(_f32c(W_grp, "W_grp")), _ptr(_f32c(b_grp, "b_grp")), n, 64, G, int(num_users), float(slope),
+                                   float(p), C.c_uint64(seed), C.c_uint64(stream_fc), C.c_uint64(stream_grp), _ptr(member),
+                                   _ptr(scores_out), _stream()), "idg_group_assign_f32")
+    return member
+
+
+def grouped_spmm_raw(csr, member, X, G, V=None, Y=None, S=None, S_in=None, x_rows=None, v_rows=None):
+    """idg_grouped_spmm_f32 on a GroupCsr: t_g[r] = sum_k values[k] [g in m(col_k)] (X_g[col_k] + V[col_k]) for g in m(r).
+    X: [n, 64] (shared by the groups) or [G, n, 64]; V: [n, 64] or None.  Y [G, n, 64] receives t_g at the rows with g in m(r)
+    (the others are NOT written), S [n, 64] receives (S_in or 0) + sum_g t_g; at least one of them; S_in may be S.
+    x_rows (shared X only) / v_rows: int32 bitmaps of the live rows of X / V — the others count as zero and are not read."""
+    who = "grouped_spmm_raw"
+    if not isinstance(csr, GroupCsr):
+        raise TypeError("%s: csr must be an ops.GroupCsr (got %s)" % (who, type(csr).__name__))
+    G, n = _check_groups(who, G), csr.n
+    for t, name in ((X, "X"), (V, "V"), (Y, "Y"), (S, "S"), (S_in, "S_in")):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("%s: %s must be float32 (got %s)" % (who, name, t.dtype))
+    for t, name in ((x_rows, "x_rows"), (v_rows, "v_rows")):
+        if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < (n + 31) // 32 or not t.is_contiguous()):
+            raise TypeError("%s: %s must be a contiguous int32 bitmap of >= %d words" % (who, name, (n + 31) // 32))
+    _check_member(who, member, n)
+    grouped = X.dim() == 3
+    if tuple(X.shape) != ((G, n, 64) if grouped else (n, 64)) or not X.is_contiguous():
+        raise ValueError("%s: X must be a contiguous [%d, 64] or [%d, %d, 64] panel, got %s" % (who, n, G, n, tuple(X.shape)))
+    for t, name in ((V, "V"), (S, "S"), (S_in, "S_in")):
+        if t is not None and (tuple(t.shape) != (n, 64) or not t.is_contiguous()):
+            raise ValueError("%s: %s must be a contiguous [%d, 64] panel, got %s" % (who, name, n, tuple(t.shape)))
+    if Y is not None and (tuple(Y.shape) != (G, n, 64) or not Y.is_contiguous()):
+        raise ValueError("%s: Y must be a contiguous [%d, %d, 64] panel, got %s" % (who, G, n, tuple(Y.shape)))
+    if Y is None and S is None:
+        raise ValueError("%s: at least one of Y and S must be given" % who)
+    if S_in is not None and S is None:
+        raise ValueError("%s: S_in without S" % who)
+    if x_rows is not None and grouped:
+        raise ValueError("%s: x_rows names the live rows of a SHARED X only" % who)
+    if v_rows is not None and V is None:
+        raise ValueError("%s: v_rows without V" % who)
+    _require_device(member, X, V, Y, S, S_in, x_rows, v_rows)
+    check(lib.idg_grouped_spmm_f32(n, csr.nnz, _ptr(csr.indptr), _ptr(csr.indices), _ptr(csr.values), 64, G, _ptr(member), _ptr(X),
+                                   n * 64 if grouped else 0, _ptr(x_rows), _ptr(V), _ptr(v_rows), _ptr(Y), n * 64, _ptr(S_in), _ptr(S),
+                                   _ptr(csr.long_rows), _ptr(csr.long_chunk0), csr.n_long, csr.n_chunks, _ptr(csr.workspace(G)),
+                                   _stream()), "idg_grouped_spmm_f32")
+    return Y, S
+
+
+def group_grad_raw(S, a, gF, b, GE, rows, out):
+    """idg_group_grad_f32: out[r] = a * S[r] + (r flagged in rows ? b * gF[r] + GE[r] : 0); S may be None (zero) or out."""
+    _require_device(S, gF, GE, rows, out)
+    n, d = out.shape
+    check(lib.idg_group_grad_f32(_ptr(S), float(a), _ptr(gF), float(b), _ptr(GE), _ptr(rows), n, d, _ptr(out), _stream()),
+          "idg_group_grad_f32")
+    return out
+
+
+class _GroupedPropagate(torch.autograd.Function):
+    """[S_1 .. S_P] (or their sum) of P chained grouped products at d = 64, S_l = sum_g X_g^l, X_g^l = A_g X_g^(l-1), X_g^0 =
+    E0.  Linear in E0 for a fixed membership and A_g symmetric, so the backward is the Horner chain through the same kernel:
+    H_g <- A_g gS_P, H_g <- A_g (gS_l + H_g) for l = P-1 .. 1, then sum_g H_g — no forward panel is kept."""
+
+    @staticmethod
+    def forward(ctx, E0, csr, member, P, G, summed):
+        n = csr.n
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=E0.device)  # noqa: E731
+        ctx.csr, ctx.member, ctx.P, ctx.G, ctx.summed = csr, member, P, G, summed
+        X, outs, S = E0, [], None
+        ping = [new(G, n, 64) if P > 2 else None, new(G, n, 64) if P > 1 else None]  # X^l goes to ping[l % 2]
+        for l in range(1, P + 1):
+            Y = ping[l % 2] if l < P else None
+            if summed:
+                S_in, S = S, (new(n, 64) if S is None else S)
+            else:
+                S_in, S = None, new(n, 64)
+                outs.append(S)
+            grouped_spmm_raw(csr, member, X, G, Y=Y, S=S, S_in=S_in)
+            X = Y
+        return S if summed else tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        csr, member, P, G = ctx.csr, ctx.member, ctx.P, ctx.G
+        n = csr.n
+        gs = [grads[0]] * P if ctx.summed else list(grads)
+        gs = [None if g is None else _f32c(g, "grad") for g in gs]
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=member.device)  # noqa: E731
+        H, ping, out = None, [None, None], None
+        for l in range(P, 0, -1):
+            g = gs[l - 1]
+            if H is None and g is None:
+                continue
+            if l > 1:
+                if ping[l % 2] is None:
+                    ping[l % 2] = new(G, n, 64)
+                Y, S = ping[l % 2], None
+            else:
+                Y, S = None, new(n, 64)
+                out = S
+            if H is None:
+                grouped_spmm_raw(csr, member, g, G, Y=Y, S=S)
+            else:
+                grouped_spmm_raw(csr, member, H, G, V=g, Y=Y, S=S)
+            H = Y
+        if out is None:
+            out = torch.zeros((n, 64), dtype=torch.float32, device=member.device)
+        return out, None, None, None, None, None
+
+
+def grouped_propagate(csr, E0, member, n_products, groups, summed=False):
+    """IMP-GCN's propagation (models/IMPGCN.py:66-81) for a fixed membership: the list [S_1 .. S_P], P = n_products =
+    GCN_layer - 1, of the group sums S_l = sum_g (D_g A D_g)^l E0 (groups ascending), or their sum when `summed`.
+    Differentiable in E0.  d = 64: idg_grouped_spmm_f32 in both directions, one walk of the adjacency per product for all
+    groups; any other width: per group, rows masked in torch, ops.spmm on csr.graph (the ops.Graph of the same matrix),
+    masked again."""
+    who = "grouped_propagate"
+    if not isinstance(csr, GroupCsr):
+        raise TypeError("%s: csr must be an ops.GroupCsr (got %s)" % (who, type(csr).__name__))
+    if E0.dtype != torch.float32:
+        raise TypeError("%s: E0 must be float32 (got %s)" % (who, E0.dtype))
+    if E0.dim() != 2 or E0.shape[0] != csr.n:
+        raise ValueError("%s: E0 must be [%d, d], got %s" % (who, csr.n, tuple(E0.shape)))
+    G = _check_groups(who, groups)
+    P = int(n_products)
+    if P < 0:
+        raise ValueError("%s: n_products = %d below 0" % (who, P))
+    _check_member(who, member, csr.n)
+    _require_device(E0, member)
+    if P == 0:
+        return torch.zeros_like(E0) if summed else []
+    if E0.shape[1] == 64:
+        out = _GroupedPropagate.apply(_f32c(E0, "E0"), csr, member, P, G, bool(summed))
+        return out if summed else list(out)
+    if csr.graph is None:
+        raise ValueError("%s: a width other than 64 (got %d) is composed through csr.graph, which this GroupCsr was made without"
+                         % (who, E0.shape[1]))
+    sums = [None] * P
+    for g in range(G):
+        mask = ((member >> g) & 1).to(torch.float32)[:, None]
+        X = E0
+        for l in range(P):
+            X = mask * spmm(csr.graph, mask * X)
+            sums[l] = X if sums[l] is None else sums[l] + X
+    if summed:
+        total = sums[0]
+        for s in sums[1:]:
+            total = total + s
+        return total
+    return sums
+
+
 # ----------------------------------------------------------------------------------- BIGCF's intent layer
 _intent_ws = {}
 

@@ -616,6 +616,57 @@ int idg_colsum_f32(const float* X, int64_t ldx, int64_t n, int64_t d, float* out
 int idg_copy_cols_f32(float* dst, int64_t ldd, const float* src, int64_t lds, int64_t n, int64_t d, void* stream);
 int idg_rows_add2_f32(float* dst, int64_t ldd, const float* a, int64_t lda, const float* b, int64_t ldb,
                       const uint32_t* rows, int64_t n, int64_t d, void* stream);
+/* IMP-GCN (models/IMPGCN.py:50-88; csrc/idg_group.hip), d = 64, fp32.
+ *
+ * idg_group_assign_f32: the group membership of every node, one launch.
+ *     temp   = keep1 * leaky_relu((ego + side) . W_fc^T + b_fc)
+ *     scores = keep2 * (temp . W_grp^T + b_grp)
+ *   W_fc [64, 64], W_grp [G, 64]: nn.Linear's [out, in] layout; 1 <= G <= 8.  keep1 is idg_ngcf_tail_f32's published mask of
+ *   (seed, stream_fc, row, feature < 64), keep2 the same function of (seed, stream_grp, row, g < G): 1 / (1 - p) where kept, 0
+ *   where dropped; p = 0: no mask.  member[r] (one byte per node) = the bitmask of { g : scores[r, g] == max_g scores[r, :] }
+ *   for r < num_users — compared by VALUE, so ties (several scores dropped to 0 over negative survivors; -0.0 against 0.0)
+ *   give several bits — and (1 << G) - 1 for r >= num_users.  scores_out (nullable, [n, G]): the masked scores exactly as the
+ *   kernel compared them.  temp is never stored; nothing is written outside member[0 .. n-1] and scores_out[0 .. n G - 1].
+ *
+ * idg_grouped_spmm_f32: one walk of a plain device CSR (indptr int64 [n + 1], indices int32 ascending per row, values fp32;
+ *   square, n x n — the arrays idg_graph_revalued_copy takes) for all G sub-graph products A_g = D_g A D_g,
+ *   D_g = diag([g in member[r]]):
+ *     t_g[r] = sum_k values[k] * [g in member[col_k]] * (X_g[col_k] + V[col_k])            for g in member[r]
+ *     Y_g[r] = t_g[r]                                   (Y nullable; group g at Y + g * y_group_stride floats)
+ *     S[r]   = (S_in ? S_in[r] : 0) + t_g[r] for g in member[r], ascending      (S nullable; S_in may BE S)
+ *   X: one shared [n, 64] panel (x_group_stride = 0) or G panels x_group_stride >= n * 64 floats apart; V (nullable): a
+ *   shared [n, 64] addend of the INPUT.  By agreement — the library's x_rows convention — row r of Y_g with g not in
+ *   member[r] is NOT written, and row c of a grouped X_g with g not in member[c] is NOT read: it may hold anything.
+ *   x_rows (nullable, a SHARED X only) / v_rows (nullable): bitmaps of the rows of X / V that are live; the others count as
+ *   zero and are not read.  A row with member 0 contributes nothing and receives nothing (its S is S_in or 0).
+ *   The order of every sum is fixed and is no function of the launch: a row's entries in chunks of IDG_GROUP_CHUNK; inside
+ *   a chunk four partial sums over the entries k = q (mod 4) in ascending k, added as (q0 + q1) + (q2 + q3); the chunks in
+ *   chunk order.  No atomics: two calls give equal bits.  long_rows [n_long] (ascending rows longer than one chunk, ALL of
+ *   them) with long_chunk0 [n_long + 1] (running count of their chunks; n_chunks in all) lets each chunk of such a row run on
+ *   a wave of its own, through ws (as many bytes as idg_grouped_spmm_workspace_bytes returns) — the same order and bits as
+ *   n_long = 0, where one wave walks the row.  Entries of the schedule that name no row or no long row are ignored.
+ *
+ * idg_group_grad_f32: out[r] = a * S[r] + (r flagged in rows ? b * gF[r] + GE[r] : 0); S nullable (counts as zero), S may BE
+ *   out.  The ego gradient of the fused step: (1 / L) * the Horner chain's sum + (G / L) * d loss / d final and the
+ *   regulariser's rows, both of which live at the batch's rows only.
+ *
+ * Any other d, NULL or misaligned pointers (panels, W_fc and ws 16 bytes; indptr 8; the rest 4), n <= 0 or >= 2^31, G outside
+ * 1 .. 8, num_users outside 0 .. n, p outside [0, 1), group strides below n * 64 or no multiple of 4, x_rows with a grouped
+ * X, v_rows without V, S_in without S, an inconsistent schedule, and outputs that overlap inputs or each other:
+ * IDG_E_INVALID before any device work. */
+#define IDG_GROUP_CHUNK 512
+int idg_group_assign_f32(const float* ego, const float* side, const float* W_fc, const float* b_fc, const float* W_grp,
+                         const float* b_grp, int64_t n, int64_t d, int G, int64_t num_users, float negative_slope, float p,
+                         uint64_t seed, uint64_t stream_fc, uint64_t stream_grp, uint8_t* member, float* scores_out, void* stream);
+int64_t idg_grouped_spmm_chunk(void);
+size_t idg_grouped_spmm_workspace_bytes(int64_t n_chunks, int G);
+int idg_grouped_spmm_f32(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices, const float* values, int64_t d, int G,
+                         const uint8_t* member, const float* X, int64_t x_group_stride, const uint32_t* x_rows, const float* V,
+                         const uint32_t* v_rows, float* Y, int64_t y_group_stride, const float* S_in, float* S,
+                         const int32_t* long_rows, const int32_t* long_chunk0, int64_t n_long, int64_t n_chunks, void* ws,
+                         void* stream);
+int idg_group_grad_f32(const float* S, float a, const float* gF, float b, const float* GE, const uint32_t* rows, int64_t n, int64_t d,
+                       float* out, void* stream);
 /* BIGCF's intent layer on rows row0 .. row0 + nrows - 1 of a panel (models/BIGCF.py:62-69; csrc/idg_intent.hip), one kernel
  * per direction, (d, k) = (64, 128), fp32:  S = X . W [., k],  P = softmax(S) (row maximum subtracted),  T = P . W^T,
  * F = X + T o Z.  Every panel, the bitmap and the noise are indexed by the GLOBAL row (the pointers are those of row 0);
