@@ -29,6 +29,40 @@ inline int fail(int code, const char* fmt, ...) {
 inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
+// ---- The aliasing checks of the entry points: which bytes a call reads or writes, and whether two such ranges meet.
+struct Span {
+  const void* ptr;
+  size_t bytes;
+};
+
+// [p, p + bytes) and [q, q + bytes2) share a byte (an absent or empty range shares none)
+inline bool overlap(const void* p, size_t bytes, const void* q, size_t bytes2) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return p && q && bytes && bytes2 && a < b + bytes2 && b < a + bytes;
+}
+
+// bytes from the first to one past the last float of an [n, d] panel read or written with leading dimension ld
+inline size_t extent(int64_t n, int64_t d, int64_t ld) { return ((size_t)(n - 1) * (size_t)ld + (size_t)d) * sizeof(float); }
+
+// does any of these outputs overlap any of these inputs / do any two of these outputs overlap
+inline bool outputs_meet_inputs(const Span* outs, int n_out, const Span* ins, int n_in) {
+  for (int o = 0; o < n_out; ++o)
+    for (int q = 0; q < n_in; ++q)
+      if (overlap(outs[o].ptr, outs[o].bytes, ins[q].ptr, ins[q].bytes)) return true;
+  return false;
+}
+inline bool outputs_meet(const Span* outs, int n_out) {
+  for (int o = 0; o < n_out; ++o)
+    for (int q = o + 1; q < n_out; ++q)
+      if (overlap(outs[o].ptr, outs[o].bytes, outs[q].ptr, outs[q].bytes)) return true;
+  return false;
+}
+
+// out[e] (+)= the sum over s of part[s * count + e], e < count, in ONE published order: lane group g of 16 adds the slices
+// g, g + 16, g + 32, ... ascending, then the 16 group sums are added g = 0 .. 15 (wgrad_reduce_kernel, idg_dense.hip: the
+// only slice reduction of the library).  `part` holds [slices][count] floats.
+int slices_reduce(const float* part, int64_t slices, int64_t count, float* out, bool accumulate, void* stream);
+
 // A row bitmap is about to be rewritten by a library call: live-unit lists registered for it (idg_graph_live_units)
 // describe its old contents and are dropped (idg_graph.hip).  bytes: extent of the write when the caller knows it (lists
 // registered for a sub-range starting inside it go too); 0 = lists registered at `bitmap` itself.

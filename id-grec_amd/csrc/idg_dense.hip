@@ -186,6 +186,13 @@ __global__ __launch_bounds__(BLOCK) void ngcf_wgrad_kernel(const float* __restri
 
 }  // namespace
 
+int idg::slices_reduce(const float* part, int64_t slices, int64_t count, float* out, bool accumulate, void* stream) {
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64 * RG), 0, (hipStream_t)stream, part, slices,
+                     count, out, accumulate ? 1 : 0);
+  IDG_HIP(hipGetLastError());
+  return IDG_OK;
+}
+
 extern "C" {
 
 size_t idg_ngcf_wgrad_workspace_bytes(int64_t d1, int64_t d2) {
@@ -203,18 +210,8 @@ int idg_ngcf_wgrad_f32(const float* side, const float* bi, const float* gT, int6
   float* part = reinterpret_cast<float*>(ws);
   hipLaunchKernelGGL(ngcf_wgrad_kernel, dim3((unsigned)slices, (unsigned)(d2 / T), (unsigned)(d1 / T)), dim3(BLOCK), 0, st, side,
                      bi, gT, n, d1, d2, part);
-  const int64_t count = 2 * d1 * d2 + 2 * d2;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64 * RG), 0, st, part, slices, count, out, 0);
-  IDG_HIP(hipGetLastError());
-  return IDG_OK;
+  return idg::slices_reduce(part, slices, 2 * d1 * d2 + 2 * d2, out, false, stream);
 }
-
-}  // extern "C"
-
-namespace {
-}  // namespace
-
-extern "C" {
 
 size_t idg_linear_wgrad_workspace_bytes(int64_t n, int64_t d1, int64_t d2) {
   if (n <= 0 || d1 <= 0 || d2 <= 0) return 0;
@@ -230,11 +227,7 @@ int idg_linear_wgrad_f32(const float* X, int64_t ldx, const float* G, int64_t ld
   float* part = reinterpret_cast<float*>(ws);
   hipLaunchKernelGGL(wgrad_partial_kernel, dim3((unsigned)s, (unsigned)((d2 + T - 1) / T), (unsigned)((d1 + T - 1) / T)),
                      dim3(BLOCK), 0, st, X, ldx, G, ldg, n, d1, d2, part);
-  const int64_t count = d1 * d2;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64 * RG), 0, st, part, s, count, w_grad,
-                     accumulate);
-  IDG_HIP(hipGetLastError());
-  return IDG_OK;
+  return idg::slices_reduce(part, s, d1 * d2, w_grad, accumulate != 0, stream);
 }
 
 }  // extern "C"
@@ -282,7 +275,7 @@ __global__ __launch_bounds__(BLOCK) void ngcf_tail_bwd_kernel(const float* __res
   const int64_t r = (int64_t)blockIdx.x * (BLOCK / 64) + threadIdx.x / 64;
   if (r >= n) return;
   // gn_rows: bitmap of the rows where gN holds anything (a fused step's d loss / d final is stored at the batch's rows only)
-  if (gN && gn_rows && !((gn_rows[r >> 5] >> (r & 31)) & 1u)) gN = nullptr;
+  if (gN && gn_rows && !idg::bit_at(gn_rows, r)) gN = nullptr;
   if (!gN && !gE) {  // nothing flows into this row
     for (int64_t f = lane; f < d; f += 64) gT[r * d + f] = 0.f;
     return;
@@ -355,7 +348,7 @@ __global__ __launch_bounds__(BLOCK) void ngcf_tail_bwd_vec_kernel(const float* _
   const int64_t r = (int64_t)blockIdx.x * (BLOCK / LPR) + threadIdx.x / LPR;
   if (r >= n) return;
   const int64_t f = 4 * l;
-  if (gN && gn_rows && !((gn_rows[r >> 5] >> (r & 31)) & 1u)) gN = nullptr;
+  if (gN && gn_rows && !idg::bit_at(gn_rows, r)) gN = nullptr;
   if (!gN && !gE) {
     *reinterpret_cast<float4*>(gT + r * d + f) = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
@@ -500,7 +493,7 @@ __global__ __launch_bounds__(BLOCK) void rows_add2_kernel(float* __restrict__ ds
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n * d4) return;
   const int64_t r = i / d4, c = i % d4;
-  if (!((rows[r >> 5] >> (r & 31)) & 1u)) return;
+  if (!idg::bit_at(rows, r)) return;
   float4 x = reinterpret_cast<float4*>(dst + r * ldd)[c];
   const float4 y = reinterpret_cast<const float4*>(a + r * lda)[c];
   x.x += y.x, x.y += y.y, x.z += y.z, x.w += y.w;
@@ -523,10 +516,7 @@ int idg_colsum_f32(const float* X, int64_t ldx, int64_t n, int64_t d, float* out
   float* part = reinterpret_cast<float*>(ws);
   hipLaunchKernelGGL(colsum_partial_kernel, dim3(CS_SLICES), dim3(BLOCK), 0, st, X, ldx, n, d, part);
   // the slices are added in slice order, 16 lane groups per 64 columns (wgrad_reduce_kernel's fixed tree)
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((d + 63) / 64)), dim3(64 * RG), 0, st, part, (int64_t)CS_SLICES, d, out,
-                     accumulate ? 1 : 0);
-  IDG_HIP(hipGetLastError());
-  return IDG_OK;
+  return idg::slices_reduce(part, CS_SLICES, d, out, accumulate != 0, stream);
 }
 
 int idg_copy_cols_f32(float* dst, int64_t ldd, const float* src, int64_t lds, int64_t n, int64_t d, void* stream) {

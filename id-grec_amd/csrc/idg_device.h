@@ -9,6 +9,9 @@ namespace idg {
 
 constexpr int WAVE = 64;
 
+// Bit r of a row bitmap (32 rows to a word, row r at bit r & 31 of word r >> 5).
+__device__ __forceinline__ bool bit_at(const uint32_t* __restrict__ bits, int64_t r) { return (bits[r >> 5] >> (r & 31)) & 1u; }
+
 // The accumulator (C/D operand) of one 32 x 32 MFMA block: 16 registers per lane.
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 

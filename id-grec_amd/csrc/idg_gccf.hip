@@ -7,18 +7,17 @@
 //   forward : side -> E = keep * (side . W + b), written with leading dimension lde (its slot of the final panel)
 //   backward: (gE, gN, side) -> gT = keep * (gE + gN at the flagged rows)   [never stored]
 //             g_side = gT . W^T,  gW = side^T . gT,  gb = column sums of gT
-// The shape is idg_ngcf.hip's: a workgroup owns 64 rows, the panel tile is read ONCE, coalesced (16 lanes x 16 bytes per
-// row), into LDS at a row stride of 68 floats (b128 operand reads of 16 rows hit 64 distinct banks); the MFMA operands
-// (v_mfma_f32_32x32x2_f32) come out of LDS, the weight operands out of registers.  Forward: one tile, 32 MFMAs per wave,
+// The shape is idg_ngcf.hip's: a workgroup owns 64 rows, the panel tile is read ONCE, coalesced, into LDS (idg_layer64.h:
+// the tile, its staging and the tile x weight product); the MFMA operands (v_mfma_f32_32x32x2_f32) come out of LDS, the
+// weight operands out of registers.  Forward: one tile, 32 MFMAs per wave,
 // the result leaves coalesced through the tile.  Backward: persistent 512-thread workgroups, two tiles (gT, side); waves
 // 0-3 form g_side while waves 4-7 add the block's share of gW / gb to accumulators that live in their registers across
 // the blocks.  The sums over rows run in a fixed order — slices of rows on the persistent workgroups, added in slice
-// order by gccf_slices_reduce_kernel: two runs give the same bits, no float atomics.
+// order by idg::slices_reduce (idg_common.h): two runs give the same bits, no float atomics.
 //
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   gccf_layer_fwd64_kernel  : 75 VGPRs, 0 AGPRs, 26 SGPRs, 17,408 bytes of LDS, scratch 0, occupancy 6 waves / SIMD
-//   gccf_layer_bwd64_kernel  : 124 VGPRs, 0 AGPRs, 73 SGPRs, 34,816 bytes of LDS, scratch 0, occupancy 4 waves / SIMD
-//   gccf_slices_reduce_kernel: 36 VGPRs, 0 AGPRs, 34 SGPRs, 4,096 bytes of LDS, scratch 0, occupancy 8 waves / SIMD
+//   gccf_layer_bwd64_kernel  : 124 VGPRs, 0 AGPRs, 75 SGPRs, 34,816 bytes of LDS, scratch 0, occupancy 4 waves / SIMD
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -26,18 +25,18 @@
 #include "idg_common.h"
 #include "idg_device.h"
 #include "idg_dropout.h"
+#include "idg_layer64.h"
 
 namespace {
 
 using idg::f32x16;
+using idg::layer64::LDT;
+using idg::layer64::RB;
 
 constexpr int BLOCK = 256;
 constexpr int D = 64;
-constexpr int RB = 64;   // rows per workgroup tile
-constexpr int LDT = 68;  // LDS row stride in floats: rows 16-byte aligned, b128 operand reads of 16 rows hit 64 distinct banks
 constexpr int BWD_BLOCK = 512;
 constexpr int BWD_WGS = 512;  // resident workgroups of the backward kernel (2 x 512 threads per CU) = most slices of its sums
-constexpr int RG = 16;
 constexpr int64_t WCOUNT = D * D + D;  // [gW | gb]
 
 __global__ __launch_bounds__(BLOCK, 4) void gccf_layer_fwd64_kernel(const float* __restrict__ side, const float* __restrict__ W,
@@ -48,29 +47,11 @@ __global__ __launch_bounds__(BLOCK, 4) void gccf_layer_fwd64_kernel(const float*
   const int rt = w >> 1, ct = w & 1;  // this wave's 32 x 32 tile of the 64 x 64 block
   const int64_t r0 = (int64_t)blockIdx.x * RB;
   // the wave's 32 weights per lane (column 32 ct + i, K-values 32 h ...): issued first, in flight across the staging
-  float wr[32];
-#pragma unroll
-  for (int s = 0; s < 32; ++s) wr[s] = W[(32 * h + s) * D + 32 * ct + i];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int e = tid + BLOCK * j, rr = e >> 4, c4 = (e & 15) * 4;
-    const int64_t row = r0 + rr < n ? r0 + rr : n - 1;  // rows past the end read the last row (and are not written)
-    *reinterpret_cast<float4*>(s_t + rr * LDT + c4) = *reinterpret_cast<const float4*>(side + row * D + c4);
-  }
+  f32x16 wr[2];
+  idg::layer64::load_w_col(W, D, 32 * ct + i, h, wr[0], wr[1]);
+  idg::layer64::stage_panel<BLOCK>(s_t, side, n, r0, tid);
   __syncthreads();
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  {
-    const float* ps = s_t + (32 * rt + i) * LDT + 32 * h;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float4 x = *reinterpret_cast<const float4*>(ps + 4 * q);
-      const float xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[c], wr[4 * q + c], acc, 0, 0, 0);
-    }
-  }
+  const f32x16 acc = idg::layer64::tile_times_w<1>(s_t, rt, i, h, wr[0], wr[1]);
   __syncthreads();  // every operand has left the tile: it becomes the tile of side . W + b
   {
     const int col = 32 * ct + i;
@@ -114,11 +95,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void gccf_layer_bwd64_kernel(const fl
   f32x16 R[2];
   float cs = 0.f;
   if (input_role) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float4 u = *reinterpret_cast<const float4*>(W + (k1 + i) * D + 32 * h + 4 * q);
-      R[q >> 2][4 * (q & 3) + 0] = u.x, R[q >> 2][4 * (q & 3) + 1] = u.y, R[q >> 2][4 * (q & 3) + 2] = u.z, R[q >> 2][4 * (q & 3) + 3] = u.w;
-    }
+    idg::layer64::load_w_row(W, D, k1 + i, h, R[0], R[1]);
   } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) R[0][r] = 0.f, R[1][r] = 0.f;
@@ -138,7 +115,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void gccf_layer_bwd64_kernel(const fl
       const int rc = live ? rr : last;
       const int64_t row = r0 + rc;
       *reinterpret_cast<float4*>(s_side + rr * LDT + c4) = *reinterpret_cast<const float4*>(side_b + (rc * D + c4));
-      const bool has_n = gN && (!gn_rows || ((gn_rows[row >> 5] >> (row & 31)) & 1u));
+      const bool has_n = gN && (!gn_rows || idg::bit_at(gn_rows, row));
       float out[4] = {0.f, 0.f, 0.f, 0.f};
       if (live && (has_n || gE)) {  // (the 16 lanes of a row decide alike)
         float g[4] = {0.f, 0.f, 0.f, 0.f};
@@ -160,17 +137,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void gccf_layer_bwd64_kernel(const fl
     __syncthreads();
     if (input_role) {
       // ---- g_side = gT . W^T
-      const float* pg = s_g + (32 * rt + i) * LDT + 32 * h;
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float4 x = *reinterpret_cast<const float4*>(pg + 4 * q);
-        const float xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[c], R[q >> 2][4 * (q & 3) + c], acc, 0, 0, 0);
-      }
+      const f32x16 acc = idg::layer64::tile_times_w<1>(s_g, rt, i, h, R[0], R[1]);
       float* gs_b = gSide + r0 * D;  // (a register's 32 lanes of one row: one 128-byte line)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -199,39 +166,6 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void gccf_layer_bwd64_kernel(const fl
   if (mt == 0 && h == 0) out[D * D + 32 * nt + i] = cs;
 }
 
-// out[e] = sum over the slices, in slice order (RG partial sums of interleaved slices, then those in order)
-__global__ __launch_bounds__(64 * RG) void gccf_slices_reduce_kernel(const float* __restrict__ part, int64_t slices, int64_t count,
-                                                                     float* __restrict__ out) {
-  __shared__ float s_sum[RG][64];
-  const int lane = threadIdx.x % 64, g = threadIdx.x / 64;
-  const int64_t e = (int64_t)blockIdx.x * 64 + lane;
-  float t = 0.f;
-  if (e < count) {
-    for (int64_t s0 = g; s0 < slices; s0 += 8 * RG) {  // eight independent loads in flight, added in slice order
-      float v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = s0 + q * RG < slices ? part[(s0 + q * RG) * count + e] : 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) t += v[q];
-    }
-  }
-  s_sum[g][lane] = t;
-  __syncthreads();
-  if (g == 0 && e < count) {
-    t = s_sum[0][lane];
-    for (int q = 1; q < RG; ++q) t += s_sum[q][lane];
-    out[e] = t;
-  }
-}
-
-bool overlap(const void* p, size_t bytes, const void* q, size_t bytes2) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return p && q && a < b + bytes2 && b < a + bytes;
-}
-
-// bytes from the first to one past the last float of an [n, d] panel read or written with leading dimension ld
-size_t extent(int64_t n, int64_t d, int64_t ld) { return ((size_t)(n - 1) * (size_t)ld + (size_t)d) * sizeof(float); }
-
 }  // namespace
 
 extern "C" {
@@ -247,9 +181,8 @@ int idg_gccf_layer_fwd_f32(const float* side, const float* W, const float* b, in
   IDG_REQUIRE(p >= 0.f && p < 1.f, "idg_gccf_layer_fwd_f32: drop probability p = %g outside [0, 1)", (double)p);
   IDG_REQUIRE(((uintptr_t)side | (uintptr_t)E) % 16 == 0 && ((uintptr_t)W | (uintptr_t)b) % 4 == 0,
               "idg_gccf_layer_fwd_f32: misaligned argument (panels 16 bytes, W and b 4 bytes)");
-  const size_t panel = extent(n, d, d), out = extent(n, d, lde);
-  IDG_REQUIRE(!overlap(E, out, side, panel) && !overlap(E, out, W, sizeof(float) * D * D) && !overlap(E, out, b, sizeof(float) * D),
-              "idg_gccf_layer_fwd_f32: E overlaps an input");
+  const idg::Span out = {E, idg::extent(n, d, lde)}, ins[3] = {{side, idg::extent(n, d, d)}, {W, sizeof(float) * D * D}, {b, sizeof(float) * D}};
+  IDG_REQUIRE(!idg::outputs_meet_inputs(&out, 1, ins, 3), "idg_gccf_layer_fwd_f32: E overlaps an input");
   hipLaunchKernelGGL(gccf_layer_fwd64_kernel, dim3((unsigned)((n + RB - 1) / RB)), dim3(BLOCK), 0, (hipStream_t)stream, side, W, b, n,
                      p, seed, stream_id, E, lde);
   IDG_HIP(hipGetLastError());
@@ -274,17 +207,13 @@ int idg_gccf_layer_bwd_f32(const float* gE, const float* gN, int64_t ldgn, const
   IDG_REQUIRE(((uintptr_t)gE | (uintptr_t)gN | (uintptr_t)side | (uintptr_t)W | (uintptr_t)g_side) % 16 == 0 &&
                   ((uintptr_t)gn_rows | (uintptr_t)w_grads | (uintptr_t)ws) % 4 == 0,
               "idg_gccf_layer_bwd_f32: misaligned argument (panels and W 16 bytes, gn_rows, w_grads and ws 4 bytes)");
-  const size_t panel = extent(n, d, d), gnb = gN ? extent(n, d, ldgn) : 0, wb = sizeof(float) * D * D;
+  const size_t panel = idg::extent(n, d, d), gnb = gN ? idg::extent(n, d, ldgn) : 0, wb = sizeof(float) * D * D;
   const size_t bits = (size_t)((n + 31) / 32) * sizeof(uint32_t), wg = sizeof(float) * WCOUNT;
   const size_t wsb = idg_gccf_layer_bwd_workspace_bytes(d);
-  const struct { const void* ptr; size_t bytes; } outs[3] = {{g_side, panel}, {w_grads, wg}, {ws, wsb}},
-                                                  ins[5] = {{gE, panel}, {gN, gnb}, {gn_rows, bits}, {side, panel}, {W, wb}};
-  for (int o = 0; o < 3; ++o) {
-    for (int q = 0; q < 5; ++q)
-      IDG_REQUIRE(!overlap(outs[o].ptr, outs[o].bytes, ins[q].ptr, ins[q].bytes), "idg_gccf_layer_bwd_f32: an output overlaps an input");
-    for (int q = o + 1; q < 3; ++q)
-      IDG_REQUIRE(!overlap(outs[o].ptr, outs[o].bytes, outs[q].ptr, outs[q].bytes), "idg_gccf_layer_bwd_f32: two outputs overlap");
-  }
+  const idg::Span outs[3] = {{g_side, panel}, {w_grads, wg}, {ws, wsb}},
+                  ins[5] = {{gE, panel}, {gN, gnb}, {gn_rows, bits}, {side, panel}, {W, wb}};
+  IDG_REQUIRE(!idg::outputs_meet_inputs(outs, 3, ins, 5), "idg_gccf_layer_bwd_f32: an output overlaps an input");
+  IDG_REQUIRE(!idg::outputs_meet(outs, 3), "idg_gccf_layer_bwd_f32: two outputs overlap");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n_blocks = (n + RB - 1) / RB;
   // two resident workgroups on EVERY CU (a count in between leaves some CUs with one workgroup and some with two)
@@ -292,9 +221,7 @@ int idg_gccf_layer_bwd_f32(const float* gE, const float* gN, int64_t ldgn, const
   float* part = reinterpret_cast<float*>(ws);
   hipLaunchKernelGGL(gccf_layer_bwd64_kernel, dim3((unsigned)wgs), dim3(BWD_BLOCK), 0, st, gE, gN, ldgn, gn_rows, side, W, n, p, seed,
                      stream_id, g_side, part);
-  hipLaunchKernelGGL(gccf_slices_reduce_kernel, dim3((unsigned)((WCOUNT + 63) / 64)), dim3(64 * RG), 0, st, part, wgs, WCOUNT, w_grads);
-  IDG_HIP(hipGetLastError());
-  return IDG_OK;
+  return idg::slices_reduce(part, wgs, WCOUNT, w_grads, false, stream);
 }
 
 }  // extern "C"

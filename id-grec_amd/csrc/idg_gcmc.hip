@@ -9,9 +9,9 @@
 //             gA = gM . Wm^T,  gH = gA o LeakyReLU'(H),  g_side = gH . Wg^T
 //             gWm = A^T . gM,  gbm = column sums of gM,  gWg = side^T . gH,  gbg = column sums of gH
 //             (gM, H, A, gA, gH are never stored)
-// The shape is idg_gccf.hip's: a workgroup owns 64 rows, a panel tile is read ONCE, coalesced (16 lanes x 16 bytes per row),
-// into LDS at a row stride of 68 floats (b128 operand reads of 16 rows hit 64 distinct banks); the MFMA operands
-// (v_mfma_f32_32x32x2_f32) come out of LDS, the weight operands out of registers.  Forward: 256 threads, one tile used three
+// The shape is idg_gccf.hip's: a workgroup owns 64 rows, a panel tile is read ONCE, coalesced, into LDS (idg_layer64.h: the
+// tile, its staging and the tile x weight product); the MFMA operands (v_mfma_f32_32x32x2_f32) come out of LDS, the weight
+// operands out of registers.  Forward: 256 threads, one tile used three
 // times (side, A, M), 64 MFMAs per wave.  A product's 32 MFMA steps run as independent chains added pairwise at the end
 // (tile_times_w: two chains for H, which the backward recomputes with the same instantiation, four for M, which only the
 // forward forms): a single chain of 32 sequential float32 partial sums put T at n = 1, p = 0.9 at 8.4e-7 of its largest entry
@@ -30,13 +30,11 @@
 // gH = gA o LeakyReLU'(A) (the parameter waves hold gA in the accumulator layout of the tile of A they read) | g_side next to
 // the two parameter products.  LeakyReLU' is read off A: A > 0 iff H > 0, and the slope applies where H <= 0.
 // The sums over rows run in a fixed order — slices of rows on the persistent workgroups, added in slice order by
-// gcmc_slices_reduce_kernel (idg_gccf.hip's reduction written out again: that file's kernels are local to it): two runs give
-// the same bits, no float atomics.
+// idg::slices_reduce (idg_common.h): two runs give the same bits, no float atomics.
 //
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
-//   gcmc_layer_fwd64_kernel  : 114 VGPRs, 0 AGPRs, 26 SGPRs, 17,408 bytes of LDS, scratch 0, occupancy 4 waves / SIMD
+//   gcmc_layer_fwd64_kernel  : 111 VGPRs, 0 AGPRs, 26 SGPRs, 17,408 bytes of LDS, scratch 0, occupancy 4 waves / SIMD
 //   gcmc_layer_bwd64_kernel  : 128 VGPRs, 0 AGPRs, 90 SGPRs, 69,632 bytes of LDS, scratch 0, occupancy 4 waves / SIMD (two workgroups per CU: 139,264 of its 163,840 bytes of LDS)
-//   gcmc_slices_reduce_kernel: 36 VGPRs, 0 AGPRs, 34 SGPRs, 4,096 bytes of LDS, scratch 0, occupancy 8 waves / SIMD
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -44,49 +42,22 @@
 #include "idg_common.h"
 #include "idg_device.h"
 #include "idg_dropout.h"
+#include "idg_layer64.h"
 
 namespace {
 
 using idg::f32x16;
+using idg::layer64::LDT;
+using idg::layer64::RB;
+using idg::layer64::tile_times_w;
 
 constexpr int BLOCK = 256;
 constexpr int D = 64;
-constexpr int RB = 64;   // rows per workgroup tile
-constexpr int LDT = 68;  // LDS row stride in floats: rows 16-byte aligned, b128 operand reads of 16 rows hit 64 distinct banks
 constexpr int BWD_BLOCK = 512;
 constexpr int BWD_WGS = 512;  // resident workgroups of the backward kernel (2 x 512 threads per CU) = most slices of its sums
-constexpr int RG = 16;
 constexpr int64_t WCOUNT = 2 * (D * D + D);  // [gWg | gbg | gWm | gbm]
 constexpr int HCH = 2;  // MFMA chains of H = side . Wg (forward and the backward's recomputation: one value)
 constexpr int MCH = 4;  // ... of M = A . Wm (forward only)
-
-// (rows 32 rt ... of the tile) . (the 32 weight values per lane in w0, w1): K-values 32 h + s at step s, summed as NCH
-// independent chains of MFMAs (chain q % NCH takes the float4 groups q) that are added pairwise at the end — a shorter
-// dependent chain for the matrix core and a shorter sequential float32 sum: a chain of 32 steps carries the rounding of 32
-// partial sums, NCH chains of 32 / NCH steps and log2(NCH) additions carry that many.  ONE instantiation (NCH = 2) for the
-// forward's H and the backward's recomputed H: same operands, same order, same bits.
-template <int NCH>
-__device__ __forceinline__ f32x16 tile_times_w(const float* __restrict__ s_t, int rt, int i, int h, const f32x16& w0, const f32x16& w1) {
-  f32x16 acc[NCH];
-#pragma unroll
-  for (int k = 0; k < NCH; ++k)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-  const float* ps = s_t + (32 * rt + i) * LDT + 32 * h;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const float4 x = *reinterpret_cast<const float4*>(ps + 4 * q);
-    const float xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      acc[q % NCH] = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[c], (q < 4 ? w0 : w1)[4 * (q & 3) + c], acc[q % NCH], 0, 0, 0);
-  }
-#pragma unroll
-  for (int o = 1; o < NCH; o *= 2)
-#pragma unroll
-    for (int k = 0; k + o < NCH; k += 2 * o) acc[k] += acc[k + o];
-  return acc[0];
-}
 
 __device__ __forceinline__ float leaky(float t, float slope) { return t > 0.f ? t : t * slope; }
 
@@ -102,19 +73,12 @@ __global__ __launch_bounds__(BLOCK, 4) void gcmc_layer_fwd64_kernel(const float*
   const int64_t r0 = (int64_t)blockIdx.x * RB;
   // the wave's 32 weights per lane (column 32 ct + i, K-values 32 h ...): issued first, in flight across the staging
   f32x16 wr[2];
-#pragma unroll
-  for (int s = 0; s < 32; ++s) wr[s >> 4][s & 15] = Wg[(32 * h + s) * D + col];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int e = tid + BLOCK * j, rr = e >> 4, c4 = (e & 15) * 4;
-    const int64_t row = r0 + rr < n ? r0 + rr : n - 1;  // rows past the end read the last row (and are not written)
-    *reinterpret_cast<float4*>(s_t + rr * LDT + c4) = *reinterpret_cast<const float4*>(side + row * D + c4);
-  }
+  idg::layer64::load_w_col(Wg, D, col, h, wr[0], wr[1]);
+  idg::layer64::stage_panel<BLOCK>(s_t, side, n, r0, tid);
   __syncthreads();
   f32x16 acc = tile_times_w<HCH>(s_t, rt, i, h, wr[0], wr[1]);
   // the second product's weights: in flight across the barrier and the activation
-#pragma unroll
-  for (int s = 0; s < 32; ++s) wr[s >> 4][s & 15] = Wm[(32 * h + s) * D + col];
+  idg::layer64::load_w_col(Wm, D, col, h, wr[0], wr[1]);
   __syncthreads();  // every operand has left the tile: it becomes the tile of A = LeakyReLU(side . Wg + bg)
   {
     const float bb = bg[col];
@@ -171,17 +135,9 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void gcmc_layer_bwd64_kernel(
   // Wg (column k1 + i, K-values 32 h ...), on the parameter waves the accumulators of gWg and gWm.
   f32x16 R[4];
   float cs_g = 0.f, cs_m = 0.f, bb = 0.f;
-  {
-    const float* Wt = input_role ? Wg : Wm;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float4 u = *reinterpret_cast<const float4*>(Wt + (k1 + i) * D + 32 * h + 4 * q);
-      R[q >> 2][4 * (q & 3) + 0] = u.x, R[q >> 2][4 * (q & 3) + 1] = u.y, R[q >> 2][4 * (q & 3) + 2] = u.z, R[q >> 2][4 * (q & 3) + 3] = u.w;
-    }
-  }
+  idg::layer64::load_w_row(input_role ? Wg : Wm, D, k1 + i, h, R[0], R[1]);
   if (input_role) {
-#pragma unroll
-    for (int s = 0; s < 32; ++s) R[2 + (s >> 4)][s & 15] = Wg[(32 * h + s) * D + k1 + i];
+    idg::layer64::load_w_col(Wg, D, k1 + i, h, R[2], R[3]);
     bb = bg[k1 + i];
   } else {
 #pragma unroll
@@ -208,7 +164,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void gcmc_layer_bwd64_kernel(
       const int rc = live ? rr : last;
       const int64_t row = r0 + rc;
       *reinterpret_cast<float4*>(s_side + rr * LDT + c4) = *reinterpret_cast<const float4*>(side_b + (rc * D + c4));
-      const bool has_n = gN && (!gn_rows || ((gn_rows[row >> 5] >> (row & 31)) & 1u));
+      const bool has_n = gN && (!gn_rows || idg::bit_at(gn_rows, row));
       float out[4] = {0.f, 0.f, 0.f, 0.f};
       if (live && (has_n || gE)) {  // (the 16 lanes of a row decide alike)
         float ge[4] = {0.f, 0.f, 0.f, 0.f};
@@ -246,16 +202,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void gcmc_layer_bwd64_kernel(
       for (int r = 0; r < 16; ++r) s_a[(32 * rt + idg::mfma_c_row(r, h_l)) * LDT + k1 + i_l] = leaky(acc[r] + bb, slope);
     } else {
       // ---- gA = gM . Wm^T, kept in the accumulator
-      const float* pg = s_gm + (32 * rt + i_l) * LDT + 32 * h_l;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float4 x = *reinterpret_cast<const float4*>(pg + 4 * q);
-        const float xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[c], R[q >> 2][4 * (q & 3) + c], acc, 0, 0, 0);
-      }
+      acc = tile_times_w<1>(s_gm, rt, i_l, h_l, R[0], R[1]);
     }
     __syncthreads();
     if (!input_role) {
@@ -269,16 +216,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void gcmc_layer_bwd64_kernel(
     __syncthreads();
     if (input_role) {
       // ---- g_side = gH . Wg^T
-      const float* pg = s_gh + (32 * rt + i_l) * LDT + 32 * h_l;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float4 x = *reinterpret_cast<const float4*>(pg + 4 * q);
-        const float xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[c], R[q >> 2][4 * (q & 3) + c], acc, 0, 0, 0);
-      }
+      acc = tile_times_w<1>(s_gh, rt, i_l, h_l, R[0], R[1]);
       float* gs_b = gSide + r0 * D;  // (a register's 32 lanes of one row: one 128-byte line)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -323,44 +261,6 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void gcmc_layer_bwd64_kernel(
   }
 }
 
-// out[e] = sum over the slices, in slice order (RG partial sums of interleaved slices, then those in order)
-__global__ __launch_bounds__(64 * RG) void gcmc_slices_reduce_kernel(const float* __restrict__ part, int64_t slices, int64_t count,
-                                                                     float* __restrict__ out) {
-  __shared__ float s_sum[RG][64];
-  const int lane = threadIdx.x % 64, g = threadIdx.x / 64;
-  const int64_t e = (int64_t)blockIdx.x * 64 + lane;
-  float t = 0.f;
-  if (e < count) {
-    for (int64_t s0 = g; s0 < slices; s0 += 8 * RG) {  // eight independent loads in flight, added in slice order
-      float v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = s0 + q * RG < slices ? part[(s0 + q * RG) * count + e] : 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) t += v[q];
-    }
-  }
-  s_sum[g][lane] = t;
-  __syncthreads();
-  if (g == 0 && e < count) {
-    t = s_sum[0][lane];
-    for (int q = 1; q < RG; ++q) t += s_sum[q][lane];
-    out[e] = t;
-  }
-}
-
-bool overlap(const void* p, size_t bytes, const void* q, size_t bytes2) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return p && q && a < b + bytes2 && b < a + bytes;
-}
-
-// bytes from the first to one past the last float of an [n, d] panel read or written with leading dimension ld
-size_t extent(int64_t n, int64_t d, int64_t ld) { return ((size_t)(n - 1) * (size_t)ld + (size_t)d) * sizeof(float); }
-
-struct Span {
-  const void* ptr;
-  size_t bytes;
-};
-
 }  // namespace
 
 extern "C" {
@@ -378,12 +278,10 @@ int idg_gcmc_layer_fwd_f32(const float* side, const float* Wg, const float* bg, 
   IDG_REQUIRE(((uintptr_t)side | (uintptr_t)T | (uintptr_t)N) % 16 == 0 &&
                   ((uintptr_t)Wg | (uintptr_t)bg | (uintptr_t)Wm | (uintptr_t)bm) % 4 == 0,
               "idg_gcmc_layer_fwd_f32: misaligned argument (panels 16 bytes, weights and biases 4 bytes)");
-  const size_t panel = extent(n, d, d), wb = sizeof(float) * D * D, bb = sizeof(float) * D;
-  const Span outs[2] = {{T, panel}, {N, extent(n, d, ldn)}}, ins[5] = {{side, panel}, {Wg, wb}, {bg, bb}, {Wm, wb}, {bm, bb}};
-  for (int o = 0; o < 2; ++o)
-    for (int q = 0; q < 5; ++q)
-      IDG_REQUIRE(!overlap(outs[o].ptr, outs[o].bytes, ins[q].ptr, ins[q].bytes), "idg_gcmc_layer_fwd_f32: an output overlaps an input");
-  IDG_REQUIRE(!overlap(outs[0].ptr, outs[0].bytes, outs[1].ptr, outs[1].bytes), "idg_gcmc_layer_fwd_f32: T and N overlap");
+  const size_t panel = idg::extent(n, d, d), wb = sizeof(float) * D * D, bb = sizeof(float) * D;
+  const idg::Span outs[2] = {{T, panel}, {N, idg::extent(n, d, ldn)}}, ins[5] = {{side, panel}, {Wg, wb}, {bg, bb}, {Wm, wb}, {bm, bb}};
+  IDG_REQUIRE(!idg::outputs_meet_inputs(outs, 2, ins, 5), "idg_gcmc_layer_fwd_f32: an output overlaps an input");
+  IDG_REQUIRE(!idg::outputs_meet(outs, 2), "idg_gcmc_layer_fwd_f32: T and N overlap");
   hipLaunchKernelGGL(gcmc_layer_fwd64_kernel, dim3((unsigned)((n + RB - 1) / RB)), dim3(BLOCK), 0, (hipStream_t)stream, side, Wg, bg,
                      Wm, bm, n, negative_slope, p, seed, stream_id, T, N, ldn);
   IDG_HIP(hipGetLastError());
@@ -410,17 +308,13 @@ int idg_gcmc_layer_bwd_f32(const float* T, const float* gE, const float* gN, int
   IDG_REQUIRE(((uintptr_t)T | (uintptr_t)gE | (uintptr_t)gN | (uintptr_t)side | (uintptr_t)Wg | (uintptr_t)Wm | (uintptr_t)g_side) % 16 == 0 &&
                   ((uintptr_t)gn_rows | (uintptr_t)bg | (uintptr_t)w_grads | (uintptr_t)ws) % 4 == 0,
               "idg_gcmc_layer_bwd_f32: misaligned argument (panels, Wg and Wm 16 bytes; gn_rows, bg, w_grads and ws 4 bytes)");
-  const size_t panel = extent(n, d, d), gnb = gN ? extent(n, d, ldgn) : 0, wb = sizeof(float) * D * D;
+  const size_t panel = idg::extent(n, d, d), gnb = gN ? idg::extent(n, d, ldgn) : 0, wb = sizeof(float) * D * D;
   const size_t bits = (size_t)((n + 31) / 32) * sizeof(uint32_t), wg = sizeof(float) * WCOUNT;
   const size_t wsb = idg_gcmc_layer_bwd_workspace_bytes(d);
-  const Span outs[3] = {{g_side, panel}, {w_grads, wg}, {ws, wsb}};
-  const Span ins[8] = {{T, panel}, {gE, panel}, {gN, gnb}, {gn_rows, bits}, {side, panel}, {Wg, wb}, {bg, sizeof(float) * D}, {Wm, wb}};
-  for (int o = 0; o < 3; ++o) {
-    for (int q = 0; q < 8; ++q)
-      IDG_REQUIRE(!overlap(outs[o].ptr, outs[o].bytes, ins[q].ptr, ins[q].bytes), "idg_gcmc_layer_bwd_f32: an output overlaps an input");
-    for (int q = o + 1; q < 3; ++q)
-      IDG_REQUIRE(!overlap(outs[o].ptr, outs[o].bytes, outs[q].ptr, outs[q].bytes), "idg_gcmc_layer_bwd_f32: two outputs overlap");
-  }
+  const idg::Span outs[3] = {{g_side, panel}, {w_grads, wg}, {ws, wsb}};
+  const idg::Span ins[8] = {{T, panel}, {gE, panel}, {gN, gnb}, {gn_rows, bits}, {side, panel}, {Wg, wb}, {bg, sizeof(float) * D}, {Wm, wb}};
+  IDG_REQUIRE(!idg::outputs_meet_inputs(outs, 3, ins, 8), "idg_gcmc_layer_bwd_f32: an output overlaps an input");
+  IDG_REQUIRE(!idg::outputs_meet(outs, 3), "idg_gcmc_layer_bwd_f32: two outputs overlap");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n_blocks = (n + RB - 1) / RB;
   // two resident workgroups on EVERY CU (a count in between leaves some CUs with one workgroup and some with two)
@@ -428,9 +322,7 @@ int idg_gcmc_layer_bwd_f32(const float* T, const float* gE, const float* gN, int
   float* part = reinterpret_cast<float*>(ws);
   hipLaunchKernelGGL(gcmc_layer_bwd64_kernel, dim3((unsigned)wgs), dim3(BWD_BLOCK), 0, st, T, gE, gN, ldgn, gn_rows, side, Wg, bg, Wm, n,
                      negative_slope, p, seed, stream_id, g_side, part);
-  hipLaunchKernelGGL(gcmc_slices_reduce_kernel, dim3((unsigned)((WCOUNT + 63) / 64)), dim3(64 * RG), 0, st, part, wgs, WCOUNT, w_grads);
-  IDG_HIP(hipGetLastError());
-  return IDG_OK;
+  return idg::slices_reduce(part, wgs, WCOUNT, w_grads, false, stream);
 }
 
 }  // extern "C"

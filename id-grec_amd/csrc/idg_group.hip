@@ -5,10 +5,10 @@
 //      scores = keep2 * (temp . W_grp^T + b_grp)                          keep2: the same function over (row, g < G)
 //      member[r] = bitmask of { g : scores[r, g] == max_g scores[r, :] }  for r < num_users, (1 << G) - 1 for the item rows
 //    W_fc [64, 64] and W_grp [G, 64] in nn.Linear's [out, in] layout.  A workgroup owns 64 rows: ego + side is staged once,
-//    coalesced, into an LDS tile (row stride 68 floats, as idg_gcmc.hip); the 64 x 64 product runs on the matrix cores
-//    (v_mfma_f32_32x32x2_f32) as FOUR independent chains added pairwise (idg_gcmc.hip's tile_times_w written out again: that
-//    file's helpers are local to it); the activation goes back into the tile, and the d -> G product, both masks and the
-//    compare run from the tile with 16 lanes per row: temp never goes to memory.  The compare is by VALUE (-0.0 == 0.0 ties).
+//    coalesced, into an LDS tile (idg_layer64.h); the 64 x 64 product runs on the matrix cores (v_mfma_f32_32x32x2_f32)
+//    as FOUR independent chains added pairwise (that header's tile_times_w<4>); the activation goes back into the tile,
+//    and the d -> G product, both masks and the compare run from the tile with 16 lanes per row: temp never goes to
+//    memory.  The compare is by VALUE (-0.0 == 0.0 ties).
 //
 // 2. idg_grouped_spmm_f32 — ONE walk of a plain CSR for all G sub-graph products A_g = D_g A D_g, D_g = diag([g in m(r)]):
 //      t_g[r] = sum_k values[k] * [g in m(col_k)] * (X_g[col_k] + V[col_k])      for g in m(r)
@@ -43,42 +43,20 @@
 #include "idg_common.h"
 #include "idg_device.h"
 #include "idg_dropout.h"
+#include "idg_layer64.h"
 
 namespace {
 
 using idg::f32x16;
+using idg::layer64::LDT;
+using idg::layer64::RB;  // rows per workgroup tile of the assignment
 
 constexpr int BLOCK = 256;
 constexpr int D = 64;
-constexpr int RB = 64;   // rows per workgroup tile of the assignment
-constexpr int LDT = 68;  // LDS row stride in floats (idg_gcmc.hip)
 constexpr int GMAX = 8;
 constexpr int NCH = 4;   // MFMA chains of the 64 x 64 product
 constexpr int CHUNK = IDG_GROUP_CHUNK;
 constexpr int XLIVE = 0x100, VLIVE = 0x200;  // next to the 8 membership bits of an entry
-
-// (rows 32 rt ... of the tile) . (the 32 weight values per lane in w0, w1): idg_gcmc.hip's tile_times_w with NCH chains
-__device__ __forceinline__ f32x16 tile_times_w(const float* __restrict__ s_t, int rt, int i, int h, const f32x16& w0, const f32x16& w1) {
-  f32x16 acc[NCH];
-#pragma unroll
-  for (int k = 0; k < NCH; ++k)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-  const float* ps = s_t + (32 * rt + i) * LDT + 32 * h;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const float4 x = *reinterpret_cast<const float4*>(ps + 4 * q);
-    const float xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      acc[q % NCH] = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[c], (q < 4 ? w0 : w1)[4 * (q & 3) + c], acc[q % NCH], 0, 0, 0);
-  }
-#pragma unroll
-  for (int o = 1; o < NCH; o *= 2)
-#pragma unroll
-    for (int k = 0; k + o < NCH; k += 2 * o) acc[k] += acc[k + o];
-  return acc[0];
-}
 
 __global__ __launch_bounds__(BLOCK, 4) void group_assign64_kernel(const float* __restrict__ ego, const float* __restrict__ side,
                                                                const float* __restrict__ Wfc, const float* __restrict__ bfc,
@@ -94,12 +72,9 @@ __global__ __launch_bounds__(BLOCK, 4) void group_assign64_kernel(const float* _
   const int64_t r0 = (int64_t)blockIdx.x * RB;
   // B operand of temp = x . W_fc^T: B[k][col] = W_fc[col][k], K-values 32 h ... of output column `col`: 8 float4 per lane
   f32x16 wr[2];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const float4 u = *reinterpret_cast<const float4*>(Wfc + col * D + 32 * h + 4 * q);
-    wr[q >> 2][4 * (q & 3) + 0] = u.x, wr[q >> 2][4 * (q & 3) + 1] = u.y, wr[q >> 2][4 * (q & 3) + 2] = u.z, wr[q >> 2][4 * (q & 3) + 3] = u.w;
-  }
+  idg::layer64::load_w_row(Wfc, D, col, h, wr[0], wr[1]);
   for (int e = tid; e < G * D; e += BLOCK) s_wg[e] = Wgrp[e];
+  // (idg::layer64::stage_panel's loop with the sum of two panels as the value staged)
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int e = tid + BLOCK * j, rr = e >> 4, c4 = (e & 15) * 4;
@@ -109,7 +84,7 @@ __global__ __launch_bounds__(BLOCK, 4) void group_assign64_kernel(const float* _
     *reinterpret_cast<float4*>(s_t + rr * LDT + c4) = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
   }
   __syncthreads();
-  const f32x16 acc = tile_times_w(s_t, rt, i, h, wr[0], wr[1]);
+  const f32x16 acc = idg::layer64::tile_times_w<NCH>(s_t, rt, i, h, wr[0], wr[1]);
   __syncthreads();  // every operand has left the tile: it becomes the tile of leaky_relu(. + b_fc)
   {
     const float bb = bfc[col];
@@ -451,7 +426,7 @@ __global__ __launch_bounds__(BLOCK) void group_grad_kernel(const float* __restri
     const float4 s = *reinterpret_cast<const float4*>(S + 4 * e);
     o = make_float4(a * s.x, a * s.y, a * s.z, a * s.w);
   }
-  if ((rows[r >> 5] >> (r & 31)) & 1u) {
+  if (idg::bit_at(rows, r)) {
     const float4 g = *reinterpret_cast<const float4*>(gF + 4 * e);
     const float4 x = *reinterpret_cast<const float4*>(GE + 4 * e);
     o.x += b * g.x + x.x, o.y += b * g.y + x.y, o.z += b * g.z + x.z, o.w += b * g.w + x.w;
@@ -459,15 +434,8 @@ __global__ __launch_bounds__(BLOCK) void group_grad_kernel(const float* __restri
   *reinterpret_cast<float4*>(out + 4 * e) = o;
 }
 
-bool overlap(const void* p, size_t bytes, const void* q, size_t bytes2) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return p && q && bytes && bytes2 && a < b + bytes2 && b < a + bytes;
-}
-
-struct Span {
-  const void* ptr;
-  size_t bytes;
-};
+using idg::overlap;
+using idg::Span;
 
 template <int G>
 void launch_grouped(const GroupedArgs& a, const int32_t* long_rows, const int32_t* long_chunk0, int n_long, int n_chunks, float* ws,
@@ -510,10 +478,8 @@ int idg_group_assign_f32(const float* ego, const float* side, const float* W_fc,
   const Span outs[2] = {{member, (size_t)n}, {scores_out, (size_t)n * (size_t)G * sizeof(float)}};
   const Span ins[6] = {{ego, panel}, {side, panel}, {W_fc, sizeof(float) * D * D}, {b_fc, sizeof(float) * D},
                        {W_grp, sizeof(float) * D * (size_t)G}, {b_grp, sizeof(float) * (size_t)G}};
-  for (int o = 0; o < 2; ++o)
-    for (int q = 0; q < 6; ++q)
-      IDG_REQUIRE(!overlap(outs[o].ptr, outs[o].bytes, ins[q].ptr, ins[q].bytes), "idg_group_assign_f32: an output overlaps an input");
-  IDG_REQUIRE(!overlap(outs[0].ptr, outs[0].bytes, outs[1].ptr, outs[1].bytes), "idg_group_assign_f32: member and scores_out overlap");
+  IDG_REQUIRE(!idg::outputs_meet_inputs(outs, 2, ins, 6), "idg_group_assign_f32: an output overlaps an input");
+  IDG_REQUIRE(!idg::outputs_meet(outs, 2), "idg_group_assign_f32: member and scores_out overlap");
   hipLaunchKernelGGL(group_assign64_kernel, dim3((unsigned)((n + RB - 1) / RB)), dim3(BLOCK), 0, (hipStream_t)stream, ego, side, W_fc,
                      b_fc, W_grp, b_grp, n, G, num_users, negative_slope, p, seed, stream_fc, stream_grp, member, scores_out);
   IDG_HIP(hipGetLastError());
@@ -561,12 +527,8 @@ int idg_grouped_spmm_f32(int64_t n, int64_t nnz, const int64_t* indptr, const in
   const Span ins[11] = {{indptr, (size_t)(n + 1) * 8}, {indices, (size_t)nnz * 4}, {values, (size_t)nnz * 4}, {member, (size_t)n},
                         {X, xb}, {x_rows, bits}, {V, panel}, {v_rows, bits}, {long_rows, (size_t)n_long * 4},
                         {long_chunk0, (size_t)(n_long + 1) * 4}, {S_in == S ? nullptr : S_in, panel}};  // S_in may BE S (row by row)
-  for (int o = 0; o < 3; ++o) {
-    for (int q = 0; q < 11; ++q)
-      IDG_REQUIRE(!overlap(outs[o].ptr, outs[o].bytes, ins[q].ptr, ins[q].bytes), "idg_grouped_spmm_f32: an output overlaps an input");
-    for (int q = o + 1; q < 3; ++q)
-      IDG_REQUIRE(!overlap(outs[o].ptr, outs[o].bytes, outs[q].ptr, outs[q].bytes), "idg_grouped_spmm_f32: two outputs overlap");
-  }
+  IDG_REQUIRE(!idg::outputs_meet_inputs(outs, 3, ins, 11), "idg_grouped_spmm_f32: an output overlaps an input");
+  IDG_REQUIRE(!idg::outputs_meet(outs, 3), "idg_grouped_spmm_f32: two outputs overlap");
   const GroupedArgs a = {indptr, indices, values, member, X, x_group_stride, x_rows, V, v_rows, Y, y_group_stride, S_in, S, n};
   hipStream_t st = (hipStream_t)stream;
   const int nl = (int)n_long, nc = (int)n_chunks;

@@ -6,9 +6,10 @@
 //   backward: gT = gT_in (at the rows of its own bitmap, when given) + gF o Z [never stored];  gP = gT . W;  gS = P o (gP - rowsum(P o gP));
 //             gX = gF + gS . W^T;  gW = X^T . gS + gT^T . P
 // The shape is idg_gccf.hip's: a workgroup owns a tile of 64 rows (rows row0 + 64 t ...: the first row need not be
-// tile-aligned), the panel tile is read ONCE, coalesced (16 lanes x 16 bytes per row), into LDS at a row stride of 68
-// floats; S / P (and gP / gS) sit in LDS at a row stride of 132 floats (both strides: rows 16-byte aligned, b128 operand
-// reads of 16 rows hit 64 distinct banks).  The MFMA row operands (v_mfma_f32_32x32x2_f32) come out of LDS.
+// tile-aligned), the panel tile is read ONCE, coalesced (16 lanes x 16 bytes per row), into LDS at idg_layer64.h's row
+// stride of 68 floats; S / P (and gP / gS) sit in LDS at a row stride of 132 floats (for the same reason: rows 16-byte
+// aligned, b128 operand reads of 16 rows hit 64 distinct banks).  The MFMA row operands (v_mfma_f32_32x32x2_f32) come out
+// of LDS.
 //
 // Where W lives: in the waves' REGISTERS, not in LDS.  W is 32 KB; each product needs it in one of two orders — W[k-step,
 // column] for X . W and gT . W (32 registers per lane: one 32-column slice per wave), W[column, k-step] for P . W^T and
@@ -18,13 +19,12 @@
 // one LDS read per MFMA to kernels whose LDS pipe already feeds the first operand.
 //
 // gW [d, k] is a sum over rows and runs in a fixed order — row slices on the persistent workgroups, accumulators in
-// registers across a workgroup's tiles, slices added in slice order by intent_slices_reduce_kernel: two runs give the same
-// bits, no float atomics.  A tile with no flagged row is skipped; rows whose bit is clear are neither read nor written.
+// registers across a workgroup's tiles, slices added in slice order by idg::slices_reduce (idg_common.h): two runs give
+// the same bits, no float atomics.  A tile with no flagged row is skipped; rows whose bit is clear are neither read nor written.
 //
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   intent_fwd_kernel          : 242 VGPRs, 0 AGPRs, 84 SGPRs, 51,456 bytes of LDS, scratch 0, occupancy 2 waves / SIMD
 //   intent_bwd_kernel          : 244 VGPRs, 0 AGPRs, 95 SGPRs, 102,912 bytes of LDS, scratch 0, occupancy 2 waves / SIMD
-//   intent_slices_reduce_kernel: 36 VGPRs, 0 AGPRs, 34 SGPRs, 4,096 bytes of LDS, scratch 0, occupancy 8 waves / SIMD
 //   intent_noise_kernel        : 36 VGPRs, 0 AGPRs, 40 SGPRs, 0 bytes of LDS, scratch 0, occupancy 8 waves / SIMD
 // (The forward at 3 waves / SIMD — 168 VGPRs — spills 356 bytes per lane: both W orders stay in registers across the tiles,
 // so it is built for 2.)
@@ -34,27 +34,23 @@
 
 #include "idg_common.h"
 #include "idg_device.h"
+#include "idg_layer64.h"
 #include "idg_normal.h"
 
 namespace {
 
 using idg::f32x16;
+using idg::layer64::LDT;  // LDS row stride of a [64, d] tile, in floats
+using idg::layer64::RB;
 
 constexpr int D = 64;
 constexpr int K = 128;
-constexpr int RB = 64;    // rows per workgroup tile
-constexpr int LDT = 68;   // LDS row stride of a [64, d] tile, in floats
 constexpr int LDP = 132;  // LDS row stride of a [64, k] tile, in floats
 constexpr int FWD_BLOCK = 256;
 constexpr int FWD_WGS = 512;  // resident workgroups of the forward kernel (2 x 256 threads per CU: its registers allow two waves per SIMD)
 constexpr int BWD_BLOCK = 512;
 constexpr int BWD_WGS = 256;  // resident workgroups of the backward kernel (1 x 512 threads per CU: 102 KB of LDS) = most slices of gW
-constexpr int RG = 16;
 constexpr int64_t WCOUNT = D * K;
-
-__device__ __forceinline__ bool row_flag(const uint32_t* __restrict__ bits, int64_t row) {
-  return !bits || ((bits[row >> 5] >> (row & 31)) & 1u);
-}
 
 // Z of features c4 .. c4 + 3 of one global row: the panel's, or the generator's
 __device__ __forceinline__ void noise4(const float* __restrict__ noise, uint64_t seed, uint64_t stream, int64_t row, int c4, float z[4]) {
@@ -67,27 +63,13 @@ __device__ __forceinline__ void noise4(const float* __restrict__ noise, uint64_t
   }
 }
 
-// A . B over K = 64: A row 32 rt + i of an LDS tile (lane half h takes K-values 32 h ... 32 h + 31 of that row), B from
-// registers.  TWO accumulators take alternate groups of four K-steps and are added at the end: the logits reach |S| ~ 100
-// in a trained model, where every rounding of a partial sum is a relative error of 4e-6 in exp(S - max) — chains half as
-// long keep the kernels at the distance from float64 of a float32 GEMM (and the two chains issue back to back).
-__device__ __forceinline__ f32x16 mfma_k64(const float* __restrict__ pa, const float (&wr)[32]) {
-  f32x16 acc[2];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[0][r] = 0.f, acc[1][r] = 0.f;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const float4 x = *reinterpret_cast<const float4*>(pa + 4 * q);
-    const float xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[q & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[c], wr[4 * q + c], acc[q & 1], 0, 0, 0);
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[0][r] += acc[1][r];
-  return acc[0];
-}
+// S = X . W and gP = gT . W (K = 64) are idg::layer64::tile_times_w<2>: TWO chains of MFMAs take alternate groups of four
+// K-steps and are added at the end.  The logits reach |S| ~ 100 in a trained model, where every rounding of a partial sum is
+// a relative error of 4e-6 in exp(S - max) — chains half as long keep the kernels at the distance from float64 of a float32
+// GEMM (and the two chains issue back to back).
+constexpr int SCH = 2;
 
-// the same over K = 128: lane half h takes K-values 64 h ... 64 h + 63
+// The same over K = 128, for P . W^T and gS . W^T: A row of an LDS tile at pa, lane half h takes K-values 64 h ... 64 h + 63
 __device__ __forceinline__ f32x16 mfma_k128(const float* __restrict__ pa, const float (&wr)[64]) {
   f32x16 acc[2];
 #pragma unroll
@@ -117,9 +99,9 @@ __global__ __launch_bounds__(FWD_BLOCK, 2) void intent_fwd_kernel(const float* _
   const int tid = threadIdx.x, lane = tid & 63, i = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int rt = w >> 1, ct = w & 1;
-  float wa[32], wb[64];  // W[32 h + s, 32 w + i] and W[32 ct + i, 64 h + s]
-#pragma unroll
-  for (int s = 0; s < 32; ++s) wa[s] = W[(32 * h + s) * K + 32 * w + i];
+  f32x16 wa[2];  // W[32 h + s, 32 w + i]
+  float wb[64];  // W[32 ct + i, 64 h + s]
+  idg::layer64::load_w_col(W, K, 32 * w + i, h, wa[0], wa[1]);
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
     const float4 u = *reinterpret_cast<const float4*>(W + (32 * ct + i) * K + 64 * h + 4 * q);
@@ -134,7 +116,7 @@ __global__ __launch_bounds__(FWD_BLOCK, 2) void intent_fwd_kernel(const float* _
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int rr = (tid + FWD_BLOCK * j) >> 4;
-      live[j] = t0 + rr < nrows && row_flag(bits, row0 + t0 + rr);
+      live[j] = t0 + rr < nrows && (!bits || idg::bit_at(bits, row0 + t0 + rr));
       any |= live[j];
     }
     if (!__syncthreads_or(any)) continue;  // (also: the tile buffers of the previous tile are free)
@@ -149,7 +131,7 @@ __global__ __launch_bounds__(FWD_BLOCK, 2) void intent_fwd_kernel(const float* _
     // ---- S = X . W: columns 32 w + i, rows of both row tiles
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      const f32x16 acc = mfma_k64(s_x + (32 * t + i) * LDT + 32 * h, wa);
+      const f32x16 acc = idg::layer64::tile_times_w<SCH>(s_x, t, i, h, wa[0], wa[1]);
 #pragma unroll
       for (int r = 0; r < 16; ++r) s_p[(32 * t + idg::mfma_c_row(r, h)) * LDP + 32 * w + i] = acc[r];
     }
@@ -217,9 +199,9 @@ __global__ __launch_bounds__(BWD_BLOCK, 1) void intent_bwd_kernel(const float* _
   const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int rt = w8 >> 2, c4t = w8 & 3;  // S, gP: rows 32 rt ..., columns 32 c4t ...; gW: features 32 rt ... x columns 32 c4t ...
   const int xrt = (w8 >> 1) & 1, xct = w8 & 1;  // gX (waves 0-3): rows 32 xrt ..., features 32 xct ...
-  float wa[32], wb[64];
-#pragma unroll
-  for (int s = 0; s < 32; ++s) wa[s] = W[(32 * h + s) * K + 32 * c4t + i];
+  f32x16 wa[2];
+  float wb[64];
+  idg::layer64::load_w_col(W, K, 32 * c4t + i, h, wa[0], wa[1]);
   if (w8 < 4) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
@@ -241,7 +223,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 1) void intent_bwd_kernel(const float* _
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int rr = (tid + BWD_BLOCK * j) >> 4;
-      live[j] = t0 + rr < nrows && row_flag(bits, row0 + t0 + rr);
+      live[j] = t0 + rr < nrows && (!bits || idg::bit_at(bits, row0 + t0 + rr));
       any |= live[j];
     }
     if (!__syncthreads_or(any)) continue;  // (also: the tile buffers of the previous tile are free)
@@ -257,7 +239,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 1) void intent_bwd_kernel(const float* _
         float z[4];
         noise4(noise, seed, stream, row, c4, z);
         g = make_float4(f.x * z[0], f.y * z[1], f.z * z[2], f.w * z[3]);
-        if (gTin && row_flag(gt_bits, row)) {
+        if (gTin && (!gt_bits || idg::bit_at(gt_bits, row))) {
           const float4 u = *reinterpret_cast<const float4*>(gTin + row * ldgt + c4);
           g.x = u.x + g.x, g.y = u.y + g.y, g.z = u.z + g.z, g.w = u.w + g.w;
         }
@@ -269,10 +251,10 @@ __global__ __launch_bounds__(BWD_BLOCK, 1) void intent_bwd_kernel(const float* _
     __syncthreads();
     // ---- S = X . W and gP = gT . W: the wave's 32 x 32 tile of each
     {
-      f32x16 acc = mfma_k64(s_x + (32 * rt + i) * LDT + 32 * h, wa);
+      f32x16 acc = idg::layer64::tile_times_w<SCH>(s_x, rt, i, h, wa[0], wa[1]);
 #pragma unroll
       for (int r = 0; r < 16; ++r) s_p[(32 * rt + idg::mfma_c_row(r, h)) * LDP + 32 * c4t + i] = acc[r];
-      acc = mfma_k64(s_gt + (32 * rt + i) * LDT + 32 * h, wa);
+      acc = idg::layer64::tile_times_w<SCH>(s_gt, rt, i, h, wa[0], wa[1]);
 #pragma unroll
       for (int r = 0; r < 16; ++r) s_gp[(32 * rt + idg::mfma_c_row(r, h)) * LDP + 32 * c4t + i] = acc[r];
     }
@@ -329,31 +311,6 @@ __global__ __launch_bounds__(BWD_BLOCK, 1) void intent_bwd_kernel(const float* _
   for (int r = 0; r < 16; ++r) out[(32 * rt + idg::mfma_c_row(r, h)) * K + 32 * c4t + i] = gw[r];
 }
 
-// out[e] = sum over the slices, in slice order (RG partial sums of interleaved slices, then those in order)
-__global__ __launch_bounds__(64 * RG) void intent_slices_reduce_kernel(const float* __restrict__ part, int64_t slices, int64_t count,
-                                                                       float* __restrict__ out) {
-  __shared__ float s_sum[RG][64];
-  const int lane = threadIdx.x % 64, g = threadIdx.x / 64;
-  const int64_t e = (int64_t)blockIdx.x * 64 + lane;
-  float t = 0.f;
-  if (e < count) {
-    for (int64_t s0 = g; s0 < slices; s0 += 8 * RG) {  // eight independent loads in flight, added in slice order
-      float v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = s0 + q * RG < slices ? part[(s0 + q * RG) * count + e] : 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) t += v[q];
-    }
-  }
-  s_sum[g][lane] = t;
-  __syncthreads();
-  if (g == 0 && e < count) {
-    t = s_sum[0][lane];
-    for (int q = 1; q < RG; ++q) t += s_sum[q][lane];
-    out[e] = t;
-  }
-}
-
 // Z[row, f] for rows row0 .. row0 + nrows - 1 of a contiguous [., d] panel (any d): four features per thread
 __global__ __launch_bounds__(256) void intent_noise_kernel(int64_t row0, int64_t nrows, int64_t d, uint64_t seed, uint64_t stream,
                                                            float* __restrict__ out) {
@@ -363,36 +320,18 @@ __global__ __launch_bounds__(256) void intent_noise_kernel(int64_t row0, int64_t
   for (int64_t f = f0; f < f0 + 4 && f < d; ++f) out[row * d + f] = idg::normal_of(seed, stream, row, f);
 }
 
-bool overlap(const void* p, size_t bytes, const void* q, size_t bytes2) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return p && q && a < b + bytes2 && b < a + bytes;
-}
-
-struct Span {
-  const void* ptr;
-  size_t bytes;
-};
+using idg::Span;
 
 // the bytes a call touches of a panel indexed by the global row: rows row0 .. row0 + nrows - 1, d floats of each
 Span span(const float* base, int64_t row0, int64_t nrows, int64_t ld) {
   if (!base) return {nullptr, 0};
-  return {base + row0 * ld, ((size_t)(nrows - 1) * (size_t)ld + (size_t)D) * sizeof(float)};
+  return {base + row0 * ld, idg::extent(nrows, D, ld)};
 }
 
 Span bits_span(const uint32_t* bits, int64_t row0, int64_t nrows) {
   if (!bits) return {nullptr, 0};
   const int64_t w0 = row0 / 32, w1 = (row0 + nrows - 1) / 32;
   return {bits + w0, (size_t)(w1 - w0 + 1) * sizeof(uint32_t)};
-}
-
-bool clash(const Span* outs, int n_out, const Span* ins, int n_in, bool* two_outputs) {
-  for (int o = 0; o < n_out; ++o) {
-    for (int q = 0; q < n_in; ++q)
-      if (overlap(outs[o].ptr, outs[o].bytes, ins[q].ptr, ins[q].bytes)) return *two_outputs = false, true;
-    for (int q = o + 1; q < n_out; ++q)
-      if (overlap(outs[o].ptr, outs[o].bytes, outs[q].ptr, outs[q].bytes)) return *two_outputs = true, true;
-  }
-  return false;
 }
 
 bool bad_ld(int64_t ld) { return ld < D || ld % 4 != 0 || ld >= (1 << 20); }
@@ -417,9 +356,8 @@ int idg_intent_fwd_f32(const float* X, int64_t ldx, int64_t row0, int64_t nrows,
               "idg_intent_fwd_f32: misaligned argument (panels and W 16 bytes, rows_bitmap 4 bytes)");
   const Span outs[3] = {span(T, row0, nrows, ldt), span(F, row0, nrows, ldf), span(noise_out, row0, nrows, D)};
   const Span ins[4] = {span(X, row0, nrows, ldx), {W, sizeof(float) * WCOUNT}, bits_span(rows_bitmap, row0, nrows), span(noise, row0, nrows, D)};
-  bool two = false;
-  if (clash(outs, 3, ins, 4, &two))
-    return idg::fail(IDG_E_INVALID, two ? "idg_intent_fwd_f32: two outputs overlap" : "idg_intent_fwd_f32: an output overlaps an input");
+  IDG_REQUIRE(!idg::outputs_meet_inputs(outs, 3, ins, 4), "idg_intent_fwd_f32: an output overlaps an input");
+  IDG_REQUIRE(!idg::outputs_meet(outs, 3), "idg_intent_fwd_f32: two outputs overlap");
   const int64_t n_tiles = (nrows + RB - 1) / RB;
   const int64_t wgs = n_tiles < FWD_WGS ? n_tiles : FWD_WGS;
   hipLaunchKernelGGL(intent_fwd_kernel, dim3((unsigned)wgs), dim3(FWD_BLOCK), 0, (hipStream_t)stream, X, ldx, row0, nrows, W, rows_bitmap,
@@ -464,18 +402,15 @@ int idg_intent_bwd_f32(const float* gF, int64_t ldgf, const float* gT_in, int64_
   const Span ins[7] = {span(gF, row0, nrows, ldgf), span(gT_in, row0, nrows, ldgt), bits_span(rows_bitmap, row0, nrows),
                        span(X, row0, nrows, ldx),   {W, sizeof(float) * WCOUNT},    span(noise, row0, nrows, D),
                        bits_span(gT_in ? gt_rows : nullptr, row0, nrows)};
-  bool two = false;
-  if (clash(outs, 3, ins, 7, &two))
-    return idg::fail(IDG_E_INVALID, two ? "idg_intent_bwd_f32: two outputs overlap" : "idg_intent_bwd_f32: an output overlaps an input");
+  IDG_REQUIRE(!idg::outputs_meet_inputs(outs, 3, ins, 7), "idg_intent_bwd_f32: an output overlaps an input");
+  IDG_REQUIRE(!idg::outputs_meet(outs, 3), "idg_intent_bwd_f32: two outputs overlap");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n_tiles = (nrows + RB - 1) / RB;
   const int64_t wgs = n_tiles < BWD_WGS ? n_tiles : BWD_WGS;
   float* part = reinterpret_cast<float*>(ws);
   hipLaunchKernelGGL(intent_bwd_kernel, dim3((unsigned)wgs), dim3(BWD_BLOCK), 0, st, gF, ldgf, gT_in, ldgt, gt_rows, rows_bitmap, X, ldx, row0, nrows,
                      W, noise, seed, stream_id, gX, ldgx, part);
-  hipLaunchKernelGGL(intent_slices_reduce_kernel, dim3((unsigned)((WCOUNT + 63) / 64)), dim3(64 * RG), 0, st, part, wgs, WCOUNT, gW);
-  IDG_HIP(hipGetLastError());
-  return IDG_OK;
+  return idg::slices_reduce(part, wgs, WCOUNT, gW, false, stream);
 }
 
 }  // extern "C"

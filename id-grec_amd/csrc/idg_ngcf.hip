@@ -4,14 +4,16 @@
 // launches per layer that each stream the [n, 64] panels again: 47.7 us forward and 87 us backward per layer at yelp2018 size
 // (n = 69,716), a third of that spent on the address path (the MFMA operand layout reads one ROW per lane: 64 cache lines
 // per load instruction) and on launches too short to overlap their own phases.  Here a 256-thread workgroup owns 64 rows:
-// their panels are read ONCE, coalesced (16 lanes x 16 bytes per row), into padded LDS tiles; the MFMA operands come out of
-// LDS (ds_read_b128, conflict-free at a row stride of 68 floats); everything between the products — bias, LeakyReLU,
+// their panels are read ONCE, coalesced (16 lanes x 16 bytes per row), into padded LDS tiles (idg_layer64.h); the MFMA operands
+// come out of LDS (ds_read_b128, conflict-free at that header's row stride); everything between the products — bias, LeakyReLU,
 // dropout, the row norm, their derivatives — happens on the tile; results leave coalesced.
 //   forward : (side, ego) -> E = dropout(leaky(side.W1 + (ego*side).W2 + b1 + b2)), N = E / max(||E||, eps)   [S, BI never stored]
 //   backward: (E, gE, gN, side, ego) -> g_side, g_ego, and the layer's four parameter gradients                [gT never stored]
 // Same MFMA sequences and the same element arithmetic as idg_ngcf_transform_f32 / idg_ngcf_tail_ex_f32 / their backward
 // forms (idg_dense.hip): E, N, g_side and g_ego are bit-identical to the chain's; the parameter gradients are sums over the
-// rows in another (fixed) order — slices of rows on persistent workgroups, added in slice order.
+// rows in another (fixed) order — slices of rows on persistent workgroups, added in slice order (idg::slices_reduce).
+// The two-operand products below stay written out: W1's and W2's MFMAs alternate in ONE chain (forward) or feed two
+// accumulators from one pass over the tile (backward), which idg_layer64.h's one-operand product does not express.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,17 +22,17 @@
 #include "idg_common.h"
 #include "idg_device.h"
 #include "idg_dropout.h"
+#include "idg_layer64.h"
 
 namespace {
 
 using idg::f32x16;
+using idg::layer64::LDT;
+using idg::layer64::RB;
 
 constexpr int BLOCK = 256;
 constexpr int D = 64;
-constexpr int RB = 64;   // rows per workgroup tile
-constexpr int LDT = 68;  // LDS row stride in floats: rows 16-byte aligned, b128 operand reads of 16 rows hit 64 distinct banks
 constexpr int BWD_WGS = 512;  // resident workgroups of the backward kernel (2 x 512 threads per CU) = most slices of its parameter-gradient sums
-constexpr int RG = 16;
 
 __global__ __launch_bounds__(BLOCK, 4) void ngcf_layer_fwd64_kernel(const float* __restrict__ side, const float* __restrict__ ego,
                                                                  const float* __restrict__ W1, const float* __restrict__ W2,
@@ -46,13 +48,8 @@ __global__ __launch_bounds__(BLOCK, 4) void ngcf_layer_fwd64_kernel(const float*
   float w1[32], w2[32];
 #pragma unroll
   for (int s = 0; s < 32; ++s) w1[s] = W1[(32 * h + s) * D + 32 * ct + i], w2[s] = W2[(32 * h + s) * D + 32 * ct + i];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int e = tid + BLOCK * j, rr = e >> 4, c4 = (e & 15) * 4;
-    const int64_t row = r0 + rr < n ? r0 + rr : n - 1;
-    *reinterpret_cast<float4*>(s_side + rr * LDT + c4) = *reinterpret_cast<const float4*>(side + row * D + c4);
-    *reinterpret_cast<float4*>(s_ego + rr * LDT + c4) = *reinterpret_cast<const float4*>(ego + row * D + c4);
-  }
+  idg::layer64::stage_panel<BLOCK>(s_side, side, n, r0, tid);
+  idg::layer64::stage_panel<BLOCK>(s_ego, ego, n, r0, tid);
   __syncthreads();
   f32x16 acc;
 #pragma unroll
@@ -129,6 +126,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void ngcf_layer_bwd64_kernel(
   f32x16 R[4];
   float cs = 0.f;
   if (input_role) {
+    // (written out: through idg::layer64::load_w_row, once per operand, this kernel spills 188 bytes per lane)
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const float4 u = *reinterpret_cast<const float4*>(W1 + (k1 + i) * D + 32 * h + 4 * q);
@@ -165,7 +163,7 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void ngcf_layer_bwd64_kernel(
       const int64_t row = r0 + rc;
       *reinterpret_cast<float4*>(s_side + rr * LDT + c4) = *reinterpret_cast<const float4*>(side_b + (rc * D + c4));
       *reinterpret_cast<float4*>(s_ego + rr * LDT + c4) = *reinterpret_cast<const float4*>(ego_b + (rc * D + c4));
-      const bool has_n = gN && (!gn_rows || ((gn_rows[row >> 5] >> (row & 31)) & 1u));
+      const bool has_n = gN && (!gn_rows || idg::bit_at(gn_rows, row));
       float out[4] = {0.f, 0.f, 0.f, 0.f};
       if (live && (has_n || gE)) {  // (the 16 lanes of a row decide alike)
         const float4 e4 = *reinterpret_cast<const float4*>(E_b + (rc * D + c4));
@@ -258,31 +256,6 @@ __global__ __launch_bounds__(BWD_BLOCK, 4) void ngcf_layer_bwd64_kernel(
   }
 }
 
-// out[e] = sum over the slices, in slice order (RG partial sums of interleaved slices, then those in order)
-__global__ __launch_bounds__(64 * RG) void slices_reduce_kernel(const float* __restrict__ part, int64_t slices, int64_t count,
-                                                                float* __restrict__ out) {
-  __shared__ float s_sum[RG][64];
-  const int lane = threadIdx.x % 64, g = threadIdx.x / 64;
-  const int64_t e = (int64_t)blockIdx.x * 64 + lane;
-  float t = 0.f;
-  if (e < count) {
-    for (int64_t s0 = g; s0 < slices; s0 += 8 * RG) {  // eight independent loads in flight, added in slice order
-      float v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = s0 + q * RG < slices ? part[(s0 + q * RG) * count + e] : 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) t += v[q];
-    }
-  }
-  s_sum[g][lane] = t;
-  __syncthreads();
-  if (g == 0 && e < count) {
-    t = s_sum[0][lane];
-    for (int q = 1; q < RG; ++q) t += s_sum[q][lane];
-    out[e] = t;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -324,10 +297,7 @@ int idg_ngcf_layer_bwd_f32(const float* E, const float* gE, const float* gN, int
   float* part = reinterpret_cast<float*>(ws);
   hipLaunchKernelGGL(ngcf_layer_bwd64_kernel, dim3((unsigned)wgs), dim3(BWD_BLOCK), 0, st, E, gE, gN, ldgn, gn_rows, side, ego, W1, W2,
                      n, negative_slope, p, seed, stream_id, g_side, g_ego, part);
-  const int64_t count = 2 * D * D + 2 * D;
-  hipLaunchKernelGGL(slices_reduce_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64 * RG), 0, st, part, wgs, count, w_grads);
-  IDG_HIP(hipGetLastError());
-  return IDG_OK;
+  return idg::slices_reduce(part, wgs, 2 * D * D + 2 * D, w_grads, false, stream);
 }
 
 }  // extern "C"

@@ -175,11 +175,7 @@ void dispatch(const Args& p, hipStream_t st) {
     dispatch_units<false>(p, p.d, st);
 }
 
-// [p, p + bytes) and [q, q + bytes2) share a byte
-bool overlap(const void* p, size_t bytes, const void* q, size_t bytes2) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + bytes2 && b < a + bytes;
-}
+using idg::overlap;
 
 // the same panel (allowed where stated) or disjoint from it; anything in between is refused
 bool same_or_apart(const void* p, const void* q, size_t bytes) { return p == q || !overlap(p, bytes, q, bytes); }

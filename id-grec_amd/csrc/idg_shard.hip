@@ -9,13 +9,14 @@
 #include <cstdint>
 
 #include "idg_common.h"
+#include "idg_device.h"
 
 namespace {
 
 constexpr int BLOCK = 256;
 constexpr int WAVE = 64;
 
-__device__ __forceinline__ bool bit_at(const uint32_t* __restrict__ bits, int64_t r) { return (bits[r >> 5] >> (r & 31)) & 1u; }
+using idg::bit_at;
 
 // dstP[t] = idx[t] >= 0 ? srcP[idx[t]] : 0 for up to two (dst, src) panel pairs sharing one index list
 __global__ __launch_bounds__(BLOCK) void rows_gather2_kernel(float* __restrict__ dst0, const float* __restrict__ src0,
