@@ -1,4 +1,4 @@
-// Row movers and the item-row tail of the user-row-sharded training step (id-grec_amd/sharded.py).
+// Row movers and the item-row tail of the user-row-sharded training step (id-grec_amd/sharded/).
 // The reference trains on one device (utility/utility_train/trainer.py:36-56); these kernels are what sits between its
 // step's products when the user rows are cut across GPUs: the batch's user rows travel through "guest" rows, the item
 // rows a batch touches travel as compact row sets, and each rank finishes the gradient and applies Adam for the 1/N of

@@ -16,7 +16,7 @@ When to use which multi-GPU form (bench.py --parallel auto decides by the panel 
   * replicas (this file): the graph is small enough that one GPU propagates it in tens of
     microseconds (BASELINE configs 1-4: panels of 18-37 MB).  Sharding such a graph by user rows
     needs 2K+1 all-reduces of the item panel per step, each longer than the product it follows.
-  * user-row shards (sharded.py): the propagation itself is the cost (config 5: 70 ms per product
+  * user-row shards (sharded/): the propagation itself is the cost (config 5: 70 ms per product
     on one GPU) and divides across ranks.
 
 The engine is anything with `loss_and_grad(users, pos, neg) -> loss[2]`, `.grad` [n, d] and

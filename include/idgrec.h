@@ -949,7 +949,7 @@ int idg_rows_layer_mean_n_f32(float* out, const int64_t* ids, int64_t count, con
 size_t idg_flags_compact_workspace_bytes(int64_t n);
 int idg_flags_compact_f32(const float* flags, int64_t n, int64_t* ids, int64_t cap, int64_t* count, void* ws, void* stream);
 
-/* The index-only preparation of ONE global batch of the user-row-sharded step as one call (id-grec_amd/sharded.py
+/* The index-only preparation of ONE global batch of the user-row-sharded step as one call (id-grec_amd/sharded/kernels.py
  * HipKernels.prepare did this in twelve: the host cost of a step is its calls).  On `side_stream`, ordered after
  * `main_stream` through ev_fork:  users_bits = bitmap of own_users[0..n_own) (n_local_users bits); items_bits = bitmap
  * of pos[0..B) and neg[0..B) (n_items_padded bits); scatter_bits cleared (n_panel_rows bits: the gradient scatter flags
@@ -1158,7 +1158,7 @@ int idg_allgather_f32(idg_comm* comm, const float* in, float* out, int64_t count
 int idg_reduce_scatter_f32(idg_comm* comm, const float* in, float* out, int64_t count, void* stream);
 
 /* ------------------------------------------------------------------------------------
- * MULTI-GPU, opt-in: the step's panel-sized exchanges as 24-bit rows with a rank-ordered sum (id-grec_amd/sharded.py
+ * MULTI-GPU, opt-in: the step's panel-sized exchanges as 24-bit rows with a rank-ordered sum (id-grec_amd/sharded/packed.py
  * Packed24Comm; SURVEY.md 8e "fix the reduction order (rank order) so k-GPU runs are reproducible run to run").
  * An fp32 value travels as its upper 24 bits (sign, exponent, 15 mantissa bits; the dropped byte rounded to nearest even:
  * 2^-16 relative), four values in three 32-bit words — 3/4 of the bytes of the fp32 exchange.  An all-reduce becomes

@@ -1,5 +1,5 @@
 """Sizes of the row sets a batch's step reads (host, numpy): the touched items, the near / far users, the two- and
-three-hop items of id-grec_amd/sharded.py (_agree_touched_items / _agree_two_hop_items).  usage: hop_sets.py SHAPE [B]"""
+three-hop items of id-grec_amd/sharded/step.py (_agree_touched_items / _agree_two_hop_items).  usage: hop_sets.py SHAPE [B]"""
 import sys
 import time
 

@@ -1,4 +1,4 @@
-"""Worker for the world_size-2 tests of id-grec_amd/sharded.py (launched by
+"""Worker for the world_size-2 tests of id-grec_amd/sharded/ (launched by
 tests/test_sharded.py through torch.multiprocessing).  mode "cpu": the layer loop runs on
 numpy arrays with a checker-backed kernel stub (arithmetic by oracle/, TEST ONLY) over gloo;
 mode "gpu": the real HIP kernels, both ranks on cuda:0, gloo staging through the host."""

@@ -1,4 +1,4 @@
-"""User-row sharding (id-grec_amd/sharded.py): partitioner, shard extraction, and the
+"""User-row sharding (id-grec_amd/sharded/): partitioner, shard extraction, and the
 distributed step against the single-device result — world_size 2 over gloo."""
 import os
 import sys
@@ -130,6 +130,47 @@ def test_partition_is_contiguous_and_balanced():
         loads = [deg[b[r]:b[r + 1]].sum() for r in range(world)]
         assert max(loads) - min(loads) <= 2 * deg.max()
     assert sh.partition_users_by_nnz(np.zeros(5, dtype=int), 2).tolist()[0::2] == [0, 5]
+
+
+# the package's public names and the module each one lives in (id-grec_amd/sharded/__init__.py)
+SURFACE = {
+    "partition": ["partition_users_by_nnz", "shard_adjacency", "shard_adjacency_from_edges"],
+    "step": ["GlobalBatch", "ShardedEngine"],
+    "instruments": ["IssueOrder", "OrderComm", "OrderKernels", "StepTimeline", "TimelineComm", "XGMI_PEAK_GBS"],
+    "kernels": ["HipKernels"],
+    "comm": ["NativeComm", "NoComm", "TorchComm", "make_comm"],
+    "packed": ["Packed24Comm", "RankOrderComm"],
+    "driver": ["PARITY_TOL", "parity_capture", "parity_compare", "run_sharded_bench"],
+}
+
+
+def test_package_surface_and_light_import():
+    """idgrec_amd.sharded is a package that re-exports exactly the flat module's public names, each from the module that
+    owns it, and importing it loads none of torch / native / ops / synth (the gloo-on-CPU ranks and the checker-backed
+    kernel stub rely on that)."""
+    import json
+    import subprocess
+
+    import idgrec_amd.sharded as sh
+
+    names = sorted(n for mod in SURFACE.values() for n in mod)
+    assert len(names) == 22
+    assert sorted(sh.__all__) == names
+    assert all(hasattr(sh, n) for n in names)
+    child = ("import json, sys; sys.path.insert(0, %r); import idgrec_amd.sharded as sh; "
+             "heavy = [m for m in ('torch', 'idgrec_amd.native', 'idgrec_amd.ops', 'idgrec_amd.synth') if m in sys.modules]; "
+             "where = {n: getattr(getattr(sh, n), '__module__', None) for n in sh.__all__}; "
+             "const = {n: [m for m in %r if n in vars(sys.modules['idgrec_amd.sharded.' + m])] for n, w in where.items() if w is None}; "
+             "print(json.dumps([heavy, where, const]))" % (ROOT, sorted(SURFACE)))
+    out = subprocess.run([sys.executable, "-c", child], check=True, capture_output=True, text=True, cwd=ROOT).stdout
+    heavy, where, const = json.loads(out.strip().splitlines()[-1])
+    assert heavy == []
+    for mod, owned in SURFACE.items():
+        for n in owned:
+            if where[n] is not None:
+                assert where[n] == "idgrec_amd.sharded." + mod, (n, where[n])
+            else:  # a constant carries no __module__: it is a global of its own module and of no other
+                assert const[n] == [mod], (n, const[n])
 
 
 def test_global_batch_chains_and_guest_row_movers():
