@@ -120,6 +120,9 @@ PROTOTYPES = {
     "idg_table_nce_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int]),
     "idg_table_nce_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(c_vp), C.POINTER(c_vp), C.c_int64,
                                     c_vp, c_f32p, C.c_float, c_vp, c_vp, c_vp, C.POINTER(c_vp), c_vp, c_vp]),
+    "idg_mix_nce_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "idg_mix_nce_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp, c_vp, C.c_float,
+                                  C.c_float, C.c_float, C.c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "idg_kmeans_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "idg_kmeans_assign_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, c_vp, c_vp]),
     "idg_kmeans_update_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, c_vp, c_vp]),

@@ -831,6 +831,45 @@ int idg_table_nce_f32(const float* table_panel, int64_t row0, int64_t N, int64_t
                       const float* upstream, float* g_table_panel, float* const* g_query_panels, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * DEVICE: MixRec's in-batch mixing contrastive terms (Zhang et al. WWW'25; models/MixRec.py:94-154 of the reference: every
+ * term is losses.get_InfoNCE_loss_all(e1, e2, e2_all, T) whose positive e2 is NOT a row of its negative set e2_all, and
+ * whose operands exist only inside the batch), forward and backward in one call.
+ *
+ * panel [n, d], users first.  The batch's rows: u_i = panel[users[i]], p_i = panel[num_users + pos[i]],
+ * n_i = panel[num_users + neg[i]], i < B (ids may repeat).  user_perm / item_perm: DEVICE int64 [B], permutations of
+ * 0 .. B-1 (the caller's contract; an entry outside the batch reads as its own position).  nu: DEVICE float [B].
+ * hat(x) = x / max(||x||, 1e-12) (F.normalize: a zero row stays zero).
+ *
+ * A side with rows x, permutation pi and weight beta — (u, user_perm, user_beta) and (p, item_perm, item_beta):
+ *   h = hat(x),   c_i = beta x_i + (1 - beta) x_pi(i),  ch = hat(c),   m = sum_j nu_j x_j,  mh = hat(m)
+ *   D_i  = sum_j exp(h_i.h_j / T) + exp(h_i.mh / T)
+ *   side = (1/B) sum_i [ -beta log(exp(ch_i.h_i / T) / D_i + 1e-7) - (1 - beta) log(exp(ch_i.h_pi(i) / T) / D_pi(i) + 1e-7) ]
+ * which is beta InfoNCE_all(x, c, [x[pi]; m], T) + (1 - beta) InfoNCE_all(x[pi], c, [x; m], T): the first term's
+ * denominator sums over a permutation of the rows and the second term's anchors are the permuted rows, so both read one
+ * vector of row sums of one symmetric Gram matrix.
+ * The rectangular term, T = 1, with Mn_j = item_beta n_j + (1 - item_beta) n_item_perm(j):
+ *   rect = (1/B) sum_i -log( exp(hat(u)_i.hat(p)_i) / sum_j exp(hat(u)_i.hat(Mn)_j) + 1e-7 )
+ *   loss[0] = (1 - item_beta) rect                         (the reference's second list entry)
+ *   loss[1] = ssl_weight (side_users + side_items)         (its fourth)
+ * loss [2] nullable.  g_panel [n, d], nullable (NULL: losses only, the same bits as with gradients): the gradient of
+ * up[0] loss[0] + up[1] loss[1] (upstream: DEVICE [2], NULL = ones) w.r.t. the panel is ADDED into the batch's rows,
+ * repeated ids summed in batch order (users, then positives, then negatives, one launch after the other).  With
+ * kappa_k = d side / d D_k the Gram part of d side / d h_k is (1/T)[kappa_k sum_j e_kj h_j + sum_j e_kj kappa_j h_j] +
+ * (1/T) kappa_k e_km mh: two passes E.Y over the same symmetric E (Y = H, which also yields the row sums, then
+ * Y = kappa o H), no transposed pass; the rectangular term adds one transposed pass for Mn.  The mix row is one dot product
+ * per row.  Every normalisation, c, Mn and m are differentiated through (projections with double dot products).
+ * exp((s - 1) / T) stands for exp(s / T) (cosines: no running maximum).  The [B, B] matrices are never stored: 128 x 128
+ * tiles on the fp32 matrix cores (v_mfma_f32_32x32x2_f32; operands zero-padded to 32 columns: every d <= 256 one path).
+ * No float atomics, fixed summation orders: the same bits every run.  1 <= d <= 256, 1 <= B < 2^22, both betas in [0, 1].
+ * ws: idg_mix_nce_workspace_bytes, 256-byte aligned (O(chunks B d), chunks <= 64); 0 is returned for sizes not built.
+ * ---------------------------------------------------------------------------------- */
+size_t idg_mix_nce_workspace_bytes(int64_t B, int64_t d);
+int idg_mix_nce_f32(const float* panel, int64_t n, int64_t d, int64_t num_users, const int64_t* users, const int64_t* pos,
+                    const int64_t* neg, int64_t B, const int64_t* user_perm, const int64_t* item_perm, const float* nu,
+                    float user_beta, float item_beta, float temperature, float ssl_weight, float* loss, const float* upstream,
+                    float* g_panel, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * DEVICE: Lloyd's k-means, the E-step of NCL (Lin et al. WWW'22; models/NCL.py:66-81 of the reference: faiss.Kmeans on a
  * host copy of each embedding table, then index.search(x, 1) for the final assignment).
  *
