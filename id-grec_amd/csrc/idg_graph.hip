@@ -16,6 +16,8 @@
 //     16-byte loads of the dense panel row (one 4*d-byte row per LPR lanes, fully
 //     coalesced), 8 rows in flight per lane group, a strictly sequential fmaf chain per
 //     output element — the order torch's CPU sparse.mm uses, hence bit-identical to it.
+//   * the DENSE launches (every output row, dense panel) run on a second tile list over the same vrows, packed by
+//     row length instead of row number (idg_tile_packer.h), while the gathered panel is cache resident.
 //   * HBM/L2-bound: no MFMA here by design.
 #include <hip/hip_runtime.h>
 
@@ -34,6 +36,7 @@
 
 #include "idg_common.h"
 #include "idg_device.h"
+#include "idg_tile_packer.h"
 
 #ifndef IDG_ROWS_UNROLL
 #define IDG_ROWS_UNROLL 8  // panel rows in flight per lane group in the row-restricted / sparse-input kernels (few lane groups
@@ -174,6 +177,18 @@ struct idg_graph {
   // the chunk's global partial slot)
   int32_t* d_row_unit = nullptr;
   int32_t* d_slot_unit = nullptr;
+  // The length-balanced schedule of the DENSE tile launches (idg_tile_packer.h): the same vrows, LocalRows and partial
+  // slots in tiles of similar-length units, with its own tile list (banded placement when the handle has one,
+  // heaviest first otherwise), vrow pointers / targets, LocalRow table and entry list.  Built only when it can be
+  // selected (the gathered panel is cache resident at d = 64, no XL rows) and not switched off
+  // (IDG_BALANCED_TILES=0, IDG_GRAPH_NO_BALANCED); never on a masked / revalued copy.  Every restricted, sparse-input,
+  // unit-list, multi-panel and generic path runs on the schedule above.
+  int64_t n_btiles = 0;
+  Tile* d_btiles = nullptr;
+  int64_t* d_bvptr = nullptr;
+  int32_t* d_bvtgt = nullptr;
+  LocalRow* d_blocal = nullptr;
+  ColVal* d_bcv = nullptr;
   // host copies for the checker
   std::vector<int64_t> h_long_rows, h_seg_len, h_chunk_len;
 };
@@ -1554,14 +1569,24 @@ int launch_fast(const idg_graph* g, const float* X, int64_t ldx, float* partials
     // 36.9 MB panels -16 %); beyond it the two bands differ too much in miss cost (384 MB panel +9 %).
     const bool cache_resident = (int64_t)g->n_cols * d * 4 <= BAND_PANEL_BYTES;
     const Tile* tile_order = (g->d_tiles_banded && cache_resident) ? g->d_tiles_banded : (g->d_tiles_seq ? g->d_tiles_seq : g->d_tiles);
+    // The dense launches run on the length-balanced schedule when the handle carries one and the gathered panel is
+    // cache resident (the time is then loads in flight x latency: the balanced tiles keep the lane groups busy;
+    // DESIGN.md §4).  Same vrows, same partial slots, same arrival counters: same bits.
+    const bool bal = g->d_btiles != nullptr && cache_resident;
+    const dim3 dgrid((unsigned)(bal ? g->n_btiles : g->n_tiles));
+    const Tile* d_tiles = bal ? g->d_btiles : tile_order;
+    const int64_t* d_vptr = bal ? g->d_bvptr : g->d_vptr;
+    const int32_t* d_vtgt = bal ? g->d_bvtgt : g->d_vtgt;
+    const ColVal* d_cv = bal ? g->d_bcv : g->d_cv;
+    const LocalRow* d_local = bal ? g->d_blocal : g->d_local;
 #define IDG_TILE(U, DYN, MINW, EPI)                                                                            \
   do {                                                                                                         \
     if (fused_fix)                                                                                             \
-      hipLaunchKernelGGL((spmm_tile_kernel<LPR, NB, U, DYN, IDG_FUSED_MINW, EPI, true>  ), grid, block, 0, st, tile_order,  \
-                         g->d_vptr, g->d_vtgt, g->d_cv, X, ldx, partials, d, ep, fx, g->d_local);              \
+      hipLaunchKernelGGL((spmm_tile_kernel<LPR, NB, U, DYN, IDG_FUSED_MINW, EPI, true>  ), dgrid, block, 0, st, d_tiles,  \
+                         d_vptr, d_vtgt, d_cv, X, ldx, partials, d, ep, fx, d_local);                          \
     else                                                                                                       \
-      hipLaunchKernelGGL((spmm_tile_kernel<LPR, NB, U, DYN, MINW, EPI, false>  ), grid, block, 0, st,          \
-                         tile_order, g->d_vptr, g->d_vtgt, g->d_cv, X, ldx, partials, d, ep, fx, g->d_local);  \
+      hipLaunchKernelGGL((spmm_tile_kernel<LPR, NB, U, DYN, MINW, EPI, false>  ), dgrid, block, 0, st,         \
+                         d_tiles, d_vptr, d_vtgt, d_cv, X, ldx, partials, d, ep, fx, d_local);                 \
   } while (0)
     const int32_t* units = nullptr;
     int64_t ucap = 0;
@@ -2017,6 +2042,30 @@ static int graph_build(int device, int64_t n_rows, int64_t n_cols, int64_t nnz, 
   const std::vector<Tile> tiles_plain = tiles;
   std::vector<Tile> tiles_seq;
   bool banded = false;
+  std::vector<int> band;  // band of tiles_plain[t] (banded handles)
+  // tiles `tl` (heaviest first) of bands `bd` dealt to the XCDs; `seq` (optional): the bands one after the other
+  auto place_bands = [&](const std::vector<Tile>& tl, const std::vector<int>& bd, std::vector<Tile>* seq) {
+    const size_t nt = tl.size();
+    std::vector<std::vector<Tile>> by_band((size_t)bands);
+    for (size_t t = 0; t < nt; ++t) by_band[(size_t)bd[t]].push_back(tl[t]);  // keeps heaviest-first inside a band
+    if (seq)
+      for (const auto& bt : by_band) seq->insert(seq->end(), bt.begin(), bt.end());
+    std::vector<size_t> cur((size_t)bands, 0);
+    std::vector<Tile> placed;
+    placed.reserve(nt);
+    const int per = 8 / bands;
+    for (size_t p = 0; placed.size() < nt; ++p) {
+      int k = (int)((p % 8) / per);
+      if (cur[(size_t)k] >= by_band[(size_t)k].size()) {  // this band ran dry: take from the fullest remaining band
+        size_t best = 0, left = 0;
+        for (size_t q = 0; q < (size_t)bands; ++q)
+          if (by_band[q].size() - cur[q] > left) left = by_band[q].size() - cur[q], best = q;
+        k = (int)best;
+      }
+      placed.push_back(by_band[(size_t)k][cur[(size_t)k]++]);
+    }
+    return placed;
+  };
   if ((bands == 2 || bands == 4 || bands == 8) && tiles.size() >= 64) {
     banded = true;
     const size_t nt = tiles.size();
@@ -2053,29 +2102,13 @@ static int graph_build(int device, int64_t n_rows, int64_t n_cols, int64_t nnz, 
     std::vector<size_t> order(nt);
     for (size_t t = 0; t < nt; ++t) order[t] = t;
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return med[a] < med[b]; });
-    std::vector<int> band(nt, 0);
+    band.assign(nt, 0);
     int64_t acc = 0;
     for (size_t r = 0; r < nt; ++r) {
       band[order[r]] = (int)std::min<int64_t>(bands - 1, acc * bands / std::max<int64_t>(nnz, 1));
       acc += tile_nnz(tiles[order[r]]);
     }
-    std::vector<std::vector<Tile>> by_band((size_t)bands);
-    for (size_t t = 0; t < nt; ++t) by_band[(size_t)band[t]].push_back(tiles[t]);  // keeps heaviest-first inside a band
-    for (const auto& bt : by_band) tiles_seq.insert(tiles_seq.end(), bt.begin(), bt.end());
-    std::vector<size_t> cur((size_t)bands, 0);
-    std::vector<Tile> placed;
-    placed.reserve(nt);
-    const int per = 8 / bands;
-    for (size_t p = 0; placed.size() < nt; ++p) {
-      int k = (int)((p % 8) / per);
-      if (cur[(size_t)k] >= by_band[(size_t)k].size()) {  // this band ran dry: take from the fullest remaining band
-        size_t best = 0, left = 0;
-        for (size_t q = 0; q < (size_t)bands; ++q)
-          if (by_band[q].size() - cur[q] > left) left = by_band[q].size() - cur[q], best = q;
-        k = (int)best;
-      }
-      placed.push_back(by_band[(size_t)k][cur[(size_t)k]++]);
-    }
+    std::vector<Tile> placed = place_bands(tiles, band, &tiles_seq);
     tiles.swap(placed);
   }
   const std::vector<Tile>& tiles_banded = tiles;
@@ -2151,6 +2184,123 @@ static int graph_build(int device, int64_t n_rows, int64_t n_cols, int64_t nnz, 
     vrow_row.swap(vrow_row2);
   }
 
+  // ---- the length-balanced second schedule of the dense launches (idg_tile_packer.h).  The work units of the
+  // schedule above — a plain vrow, or a split row's run of segments — are packed again, by length instead of by row
+  // number, into tiles of their own; a unit keeps its band (the band of the tile it sits in above), its entries, its
+  // target (row, or global partial slot) and, for a split row, the order of its LDS slots.  Built only when the dense
+  // launches of the common widths can select it — the gathered panel is cache resident at d = 64 (wider panels take it
+  // while they are resident, launch_fast) — and every vrow fits a tile.
+  bool want_bal = (flags & IDG_GRAPH_NO_BALANCED) == 0 && xl.empty() && !tiles_plain.empty() &&
+                  n_cols * (int64_t)64 * 4 <= BAND_PANEL_BYTES;
+  if (const char* v = std::getenv("IDG_BALANCED_TILES")) want_bal = want_bal && std::atoi(v) != 0;
+  std::vector<Tile> btiles;
+  std::vector<int64_t> bvptr, bsrc;
+  std::vector<int32_t> bvtgt;
+  std::vector<LocalRow> blocals;
+  std::unique_ptr<ColVal[]> bcv_store;
+  if (want_bal) {
+    idg_pack::Limits lim = idg_pack::dense_limits();
+    lim.lslots = LSLOTS, lim.tile_vrows = TILE_VROWS;
+    if (const char* v = std::getenv("IDG_BALANCED_NNZ")) lim.tile_nnz = std::atoi(v);
+    lim.tile_nnz = std::min(std::max(64, lim.tile_nnz), TILE_NNZ);
+    if (const char* v = std::getenv("IDG_BALANCED_ROUNDS")) lim.min_rounds = std::min(std::max(1, std::atoi(v)), 64);
+    const size_t nvr = vtgt.size();
+    std::vector<int32_t> local_of(nvr, -1);  // first segment's vrow -> its LocalRow
+    for (size_t li = 0; li < locals.size(); ++li) local_of[(size_t)locals[li].vrow] = (int32_t)li;
+    struct UnitRef {
+      int32_t v, li;
+    };
+    std::vector<UnitRef> refs;
+    std::vector<idg_pack::Unit> units;
+    refs.reserve(nvr), units.reserve(nvr);
+    for (size_t ti = 0; ti < tiles_plain.size(); ++ti) {
+      const Tile& t = tiles_plain[ti];
+      for (int32_t v = t.vrow_begin; v < t.vrow_begin + t.n_vrows;) {
+        const int32_t li = local_of[(size_t)v];
+        const int32_t nseg = li >= 0 ? (int32_t)locals[(size_t)li].n_seg : 1;
+        units.push_back(idg_pack::Unit{(int32_t)(vptr[(size_t)(v + nseg)] - vptr[(size_t)v]), (int32_t)(vptr[(size_t)v + 1] - vptr[(size_t)v]),
+                                       (int16_t)nseg, (int16_t)(banded ? band[ti] : 0)});
+        refs.push_back(UnitRef{v, li});
+        v += nseg;
+      }
+    }
+    idg_pack::Packing pk;
+    idg_pack::pack(units.data(), (int64_t)units.size(), banded ? bands : 1, lim, &pk);
+    const int64_t nbt = pk.n_tiles();
+    btiles.resize((size_t)nbt);
+    std::vector<int> bband((size_t)nbt, 0);
+    {
+      int64_t pos = 0;
+      int32_t nv = 0, nl = 0;
+      for (int64_t t = 0; t < nbt; ++t) {
+        Tile bt{};
+        bt.nnz_begin = pos, bt.vrow_begin = nv, bt.local_begin = nl;
+        for (int64_t i = pk.tile_begin[(size_t)t]; i < pk.tile_begin[(size_t)t + 1]; ++i) {
+          const idg_pack::Unit& u = units[(size_t)pk.order[(size_t)i]];
+          pos += u.len, nv += u.nseg, nl += u.nseg > 1;
+        }
+        bt.n_vrows = (int16_t)(nv - bt.vrow_begin);
+        bt.n_local = (int16_t)(nl - bt.local_begin);
+        bt.row_first = 0, bt.row_last = (int32_t)std::max<int64_t>(n_rows - 1, 0);  // (no dense launch reads them)
+        bt.nnz_count = (int32_t)(pos - bt.nnz_begin);
+        bband[(size_t)t] = units[(size_t)pk.order[(size_t)pk.tile_begin[(size_t)t]]].band;
+        btiles[(size_t)t] = bt;
+      }
+      if (pos != nnz || (size_t)nv != nvr || (size_t)nl != locals.size()) {
+        delete g;
+        return idg::fail(IDG_E_INVALID, "idg_graph_create: the balanced schedule lost work (%lld of %lld entries)", (long long)pos,
+                         (long long)nnz);
+      }
+    }
+    bvptr.assign(nvr + 1, nnz);
+    bvtgt.resize(nvr);
+    blocals.resize(locals.size());
+    if (on_device) {
+      bsrc.resize(nvr);
+    } else {
+      bcv_store.reset(new (std::nothrow) ColVal[(size_t)std::max<int64_t>(nnz, 1)]);
+      if (!bcv_store) {
+        delete g;
+        return idg::fail(IDG_E_NOMEM, "idg_graph_create: out of host memory for the balanced entry list");
+      }
+    }
+    ColVal* bcv = bcv_store.get();
+    // tiles are independent of each other: ranges of tiles on worker threads
+    parallel_ranges(nbt, [&](int64_t t_lo, int64_t t_hi, int) {
+      for (int64_t t = t_lo; t < t_hi; ++t) {
+        const Tile& bt = btiles[(size_t)t];
+        int64_t pos = bt.nnz_begin;
+        int32_t nv = bt.vrow_begin, nl = bt.local_begin;
+        int lsl = 0;
+        for (int64_t i = pk.tile_begin[(size_t)t]; i < pk.tile_begin[(size_t)t + 1]; ++i) {
+          const int32_t id = pk.order[(size_t)i];
+          const UnitRef r = refs[(size_t)id];
+          const int nseg = units[(size_t)id].nseg;
+          if (r.li >= 0) blocals[(size_t)nl++] = LocalRow{locals[(size_t)r.li].tgt, nv, (int16_t)nseg, (int16_t)lsl};
+          for (int q = 0; q < nseg; ++q) {
+            const int64_t b = vptr[(size_t)(r.v + q)], e = vptr[(size_t)(r.v + q) + 1];
+            bvptr[(size_t)nv] = pos;
+            bvtgt[(size_t)nv] = r.li >= 0 ? LOCAL_CODE + lsl + q : vtgt[(size_t)r.v];
+            if (on_device) bsrc[(size_t)nv] = src_of_vrow[(size_t)(r.v + q)];
+            else std::copy(cv + b, cv + e, bcv + pos);
+            pos += e - b;
+            ++nv;
+          }
+          if (r.li >= 0) lsl += nseg;
+        }
+      }
+    }, 256);
+    // launch order: heaviest first, then the same XCD band placement as above
+    std::vector<size_t> ord((size_t)nbt);
+    for (size_t t = 0; t < ord.size(); ++t) ord[t] = t;
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return btiles[a].nnz_count > btiles[b].nnz_count; });
+    std::vector<Tile> sorted_tiles((size_t)nbt);
+    std::vector<int> sorted_band((size_t)nbt);
+    for (size_t t = 0; t < ord.size(); ++t) sorted_tiles[t] = btiles[ord[t]], sorted_band[t] = bband[ord[t]];
+    btiles = banded ? place_bands(sorted_tiles, sorted_band, nullptr) : sorted_tiles;
+    g->n_btiles = nbt;
+  }
+
   int rc = IDG_OK;
   if (nnz > 0 && !on_device) {
     rc = [&]() -> int {
@@ -2160,23 +2310,36 @@ static int graph_build(int device, int64_t n_rows, int64_t n_cols, int64_t nnz, 
     }();
   }
   if (rc == IDG_OK) rc = upload(&g->d_vptr, vptr);
-  if (rc == IDG_OK && on_device) {
-    // the (col, val) list in tile order, laid out on the device: entry k of vrow v comes from CSR position
-    // src_of_vrow[v] + (k - vptr[v])
-    rc = [&]() -> int {
-      int64_t* d_src = nullptr;
-      IDG_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_cv), (size_t)nnz * sizeof(ColVal)));
-      IDG_HIP(hipMalloc(reinterpret_cast<void**>(&d_src), src_of_vrow.size() * sizeof(int64_t)));
-      hipError_t e1 = hipMemcpyAsync(d_src, src_of_vrow.data(), src_of_vrow.size() * sizeof(int64_t), hipMemcpyHostToDevice, st);
-      if (e1 == hipSuccess) {
-        hipLaunchKernelGGL(fill_entries_kernel, dim3((unsigned)((g->n_vrows + BLOCK / 16 - 1) / (BLOCK / 16))), dim3(BLOCK), 0, st,
-                           d_indices, d_values, g->d_vptr, d_src, g->n_vrows, g->d_cv);
-        e1 = hipStreamSynchronize(st);
-      }
-      (void)hipFree(d_src);
-      IDG_HIP(e1);
-      return IDG_OK;
-    }();
+  // the (col, val) list in tile order, laid out on the device: entry k of vrow v comes from CSR position
+  // src[v] + (k - vptr[v])
+  auto fill_on_device = [&](const int64_t* d_vp, const std::vector<int64_t>& src, ColVal** d_out) -> int {
+    int64_t* d_src = nullptr;
+    IDG_HIP(hipMalloc(reinterpret_cast<void**>(d_out), (size_t)nnz * sizeof(ColVal)));
+    IDG_HIP(hipMalloc(reinterpret_cast<void**>(&d_src), src.size() * sizeof(int64_t)));
+    hipError_t e1 = hipMemcpyAsync(d_src, src.data(), src.size() * sizeof(int64_t), hipMemcpyHostToDevice, st);
+    if (e1 == hipSuccess) {
+      hipLaunchKernelGGL(fill_entries_kernel, dim3((unsigned)((g->n_vrows + BLOCK / 16 - 1) / (BLOCK / 16))), dim3(BLOCK), 0, st,
+                         d_indices, d_values, d_vp, d_src, g->n_vrows, *d_out);
+      e1 = hipStreamSynchronize(st);
+    }
+    (void)hipFree(d_src);
+    IDG_HIP(e1);
+    return IDG_OK;
+  };
+  if (rc == IDG_OK && on_device) rc = fill_on_device(g->d_vptr, src_of_vrow, &g->d_cv);
+  if (rc == IDG_OK && g->n_btiles > 0) {
+    rc = upload(&g->d_bvptr, bvptr);
+    if (rc == IDG_OK && on_device) rc = fill_on_device(g->d_bvptr, bsrc, &g->d_bcv);
+    if (rc == IDG_OK && !on_device && nnz > 0) {
+      rc = [&]() -> int {
+        IDG_HIP(hipMalloc(reinterpret_cast<void**>(&g->d_bcv), (size_t)nnz * sizeof(ColVal)));
+        IDG_HIP(hipMemcpy(g->d_bcv, bcv_store.get(), (size_t)nnz * sizeof(ColVal), hipMemcpyHostToDevice));
+        return IDG_OK;
+      }();
+    }
+    if (rc == IDG_OK) rc = upload(&g->d_bvtgt, bvtgt);
+    if (rc == IDG_OK) rc = upload(&g->d_blocal, blocals);
+    if (rc == IDG_OK) rc = upload(&g->d_btiles, btiles);  // (last: a dense launch selects the schedule by this pointer)
   }
   if (rc == IDG_OK) rc = upload(&g->d_vtgt, vtgt);
   if (rc == IDG_OK) rc = upload(&g->d_tiles, tiles_plain);
@@ -2273,6 +2436,11 @@ int idg_graph_destroy(idg_graph* g) {
         (void)hipFree(g->d_vrow_row);
         (void)hipFree(g->d_row_unit);
         (void)hipFree(g->d_slot_unit);
+        (void)hipFree(g->d_btiles);
+        (void)hipFree(g->d_bvptr);
+        (void)hipFree(g->d_bvtgt);
+        (void)hipFree(g->d_blocal);
+        (void)hipFree(g->d_bcv);
       }
     }
   }
@@ -2351,6 +2519,9 @@ static int graph_copy_shell(const idg_graph* g, idg_graph** out, const char* who
   c->borrowed = true;
   c->d_cv = nullptr;
   c->d_long_cnt = nullptr;
+  // a copy has its own values in the base's entry order only: it runs on the base's first schedule
+  c->n_btiles = 0;
+  c->d_btiles = nullptr, c->d_bvptr = nullptr, c->d_bvtgt = nullptr, c->d_blocal = nullptr, c->d_bcv = nullptr;
   int rc = IDG_OK;
   if (g->nnz > 0 && hipMalloc(reinterpret_cast<void**>(&c->d_cv), (size_t)g->nnz * sizeof(ColVal)) != hipSuccess)
     rc = idg::fail(IDG_E_NOMEM, "%s: hipMalloc of %lld entries failed", who, (long long)g->nnz);
@@ -2503,11 +2674,46 @@ int idg_graph_info(const idg_graph* g, int64_t info[8]) {
   info[0] = g->n_rows;
   info[1] = g->n_cols;
   info[2] = g->nnz;
-  info[3] = g->n_tiles + g->n_xl;
+  info[3] = (g->d_btiles ? g->n_btiles : g->n_tiles) + g->n_xl;  // workgroups of a dense launch (a cache-resident panel)
   info[4] = g->n_split;
   info[5] = g->n_slots;
   info[6] = g->split_threshold;
   info[7] = g->flags;
+  return IDG_OK;
+}
+
+// tiles, rounds and 16 x makespan of one schedule, from its device tables (a diagnostic: blocking copies)
+static int schedule_stats(const idg_graph* g, const Tile* d_tiles, int64_t n_tiles, const int64_t* d_vptr, int64_t out[3]) {
+  out[0] = n_tiles, out[1] = 0, out[2] = 0;
+  if (n_tiles <= 0 || !d_tiles || !d_vptr) return IDG_OK;
+  std::vector<Tile> tiles((size_t)n_tiles);
+  std::vector<int64_t> vptr((size_t)g->n_vrows + 1);
+  IDG_HIP(hipMemcpy(tiles.data(), d_tiles, tiles.size() * sizeof(Tile), hipMemcpyDeviceToHost));
+  IDG_HIP(hipMemcpy(vptr.data(), d_vptr, vptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+  const idg_pack::Limits lim;
+  for (const Tile& t : tiles) {
+    const int64_t* p = vptr.data() + t.vrow_begin;
+    for (int v = 0; v < t.n_vrows; ++v) out[1] += idg_pack::rounds_of(p[v + 1] - p[v], lim.unroll);
+    out[2] += (int64_t)lim.groups * idg_pack::list_makespan(t.n_vrows, [&](int64_t v) { return p[v + 1] - p[v]; }, lim.groups, lim.unroll);
+  }
+  return IDG_OK;
+}
+
+int idg_graph_schedule_info(const idg_graph* g, int64_t info[8]) {
+  IDG_REQUIRE(g && info, "idg_graph_schedule_info: NULL argument");
+  DeviceGuard guard;
+  int rc = guard.enter(g->device);
+  if (rc != IDG_OK) return rc;
+  const int64_t per_vrow = (int64_t)(sizeof(int64_t) + sizeof(int32_t));
+  rc = schedule_stats(g, g->d_tiles, g->n_tiles, g->d_vptr, info);
+  if (rc != IDG_OK) return rc;
+  info[3] = g->nnz * (int64_t)sizeof(ColVal) + g->n_vrows * per_vrow + g->n_tiles * (int64_t)sizeof(Tile) +
+            g->n_local * (int64_t)sizeof(LocalRow);
+  rc = schedule_stats(g, g->d_btiles, g->n_btiles, g->d_bvptr, info + 4);
+  if (rc != IDG_OK) return rc;
+  info[7] = g->d_btiles ? g->nnz * (int64_t)sizeof(ColVal) + g->n_vrows * per_vrow + g->n_btiles * (int64_t)sizeof(Tile) +
+                              g->n_local * (int64_t)sizeof(LocalRow)
+                        : 0;
   return IDG_OK;
 }
 

@@ -53,6 +53,7 @@ PROTOTYPES = {
     "idg_graph_remask": (C.c_int, [c_vp, c_vp, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.c_int, c_vp]),
     "idg_graph_masked_copy": (C.c_int, [c_vp, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.c_int, c_vp, C.POINTER(c_vp)]),
     "idg_graph_info": (C.c_int, [c_vp, c_i64p]),
+    "idg_graph_schedule_info": (C.c_int, [c_vp, c_i64p]),
     "idg_graph_forget_units_ws": (C.c_int, [c_vp]),
     "idg_graph_compact_inputs_bytes": (C.c_size_t, [c_vp]),
     "idg_graph_compact_inputs": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
@@ -241,6 +242,7 @@ IDG_NLL_STATS_READY = 1  # idg_multinomial_nll_f32 flags: the row statistics in 
 IDG_TNCE_MAX_QUERY_BLOCKS = 4  # idg_table_nce_f32: query blocks one call takes
 IDG_GRAPH_SYMMETRIC = 1
 IDG_GRAPH_EXACT_ORDER = 2
+IDG_GRAPH_NO_BALANCED = 4  # no length-balanced second tile schedule for the dense launches (speed only)
 
 
 IDG_STEP_SLOTS, IDG_STEP_STORE_GRAD, IDG_STEP_PACED = 3, 1, 2

@@ -86,7 +86,7 @@ class Graph:
     """
 
     def __init__(self, indptr, indices, values, n_rows, n_cols, device=None, symmetric=True, exact_order=False,
-                 split_threshold=0, build_transpose=True, _transpose_of=None):
+                 split_threshold=0, build_transpose=True, _transpose_of=None, balanced_tiles=True):
         if not torch.cuda.is_available():
             raise RuntimeError("idgrec_amd.Graph needs a HIP device (torch.cuda.is_available() is False); "
                                "this library has no CPU path.")
@@ -100,7 +100,8 @@ class Graph:
         values = np.ascontiguousarray(values, dtype=np.float32)
         self.nnz = int(indices.shape[0])
         self.symmetric = bool(symmetric)
-        flags = (native.IDG_GRAPH_SYMMETRIC if symmetric else 0) | (native.IDG_GRAPH_EXACT_ORDER if exact_order else 0)
+        flags = (native.IDG_GRAPH_SYMMETRIC if symmetric else 0) | (native.IDG_GRAPH_EXACT_ORDER if exact_order else 0) \
+            | (0 if balanced_tiles else native.IDG_GRAPH_NO_BALANCED)
         h = C.c_void_p()
         check(lib.idg_graph_create(self.device.index, self.n_rows, self.n_cols, self.nnz,
                                    native.np_ptr(indptr, C.c_int64), native.np_ptr(indices, C.c_int32),
@@ -116,10 +117,10 @@ class Graph:
             At.sort_indices()
             self._T = Graph(At.indptr, At.indices, At.data, self.n_cols, self.n_rows, device=self.device,
                             symmetric=False, exact_order=exact_order, split_threshold=split_threshold,
-                            _transpose_of=self)
+                            _transpose_of=self, balanced_tiles=balanced_tiles)
 
     @classmethod
-    def from_torch_sparse(cls, t, symmetric=True, exact_order=False, split_threshold=0):
+    def from_torch_sparse(cls, t, symmetric=True, exact_order=False, split_threshold=0, balanced_tiles=True):
         """From the reference's own operand: a coalesced sparse COO (or CSR) fp32 tensor that lives on the device
         (models/LightGCN.py:31-32: convert_sp_mat_to_sp_tensor(...).coalesce().to(device)) — idg_graph_create_from_device.
         Non-symmetric graphs get no transposed handle here (build it from t.t().coalesce())."""
@@ -132,7 +133,8 @@ class Graph:
         g = cls.__new__(cls)
         g.device, (g.n_rows, g.n_cols), g.nnz = t.device, (int(t.shape[0]), int(t.shape[1])), int(col.shape[0])
         g.symmetric, g._ws, g._T = bool(symmetric), {}, None
-        flags = (native.IDG_GRAPH_SYMMETRIC if symmetric else 0) | (native.IDG_GRAPH_EXACT_ORDER if exact_order else 0)
+        flags = (native.IDG_GRAPH_SYMMETRIC if symmetric else 0) | (native.IDG_GRAPH_EXACT_ORDER if exact_order else 0) \
+            | (0 if balanced_tiles else native.IDG_GRAPH_NO_BALANCED)
         h = C.c_void_p()
         with torch.cuda.device(t.device):
             check(lib.idg_graph_create_from_device(t.device.index, g.n_rows, g.n_cols, g.nnz, _ptr(crow), _ptr(col), _ptr(val),
@@ -261,6 +263,19 @@ class Graph:
         check(lib.idg_graph_info(self._h, a), "idg_graph_info")
         keys = ("n_rows", "n_cols", "nnz", "n_tiles", "n_long_rows", "n_segments", "split_threshold", "flags")
         return dict(zip(keys, [int(x) for x in a]))
+
+    def schedule_info(self):
+        """idg_graph_schedule_info: {"base": {...}, "balanced": {...}} with tiles, rounds, slots (16 x makespan summed over
+        the tiles), bytes and utilisation = rounds / slots of the handle's two tile schedules (balanced: zeros when the
+        handle carries none).  Reads the schedule back from the device."""
+        a = (C.c_int64 * 8)()
+        check(lib.idg_graph_schedule_info(self._h, a), "idg_graph_schedule_info")
+        out = {}
+        for name, o in (("base", 0), ("balanced", 4)):
+            tiles, rounds, slots, nbytes = (int(a[o + k]) for k in range(4))
+            out[name] = {"tiles": tiles, "rounds": rounds, "slots": slots, "bytes": nbytes,
+                         "utilisation": rounds / slots if slots else 0.0}
+        return out
 
     def long_rows(self):
         n = self.info()["n_long_rows"]

@@ -129,6 +129,9 @@ typedef struct idg_graph idg_graph;
 #define IDG_GRAPH_SYMMETRIC 1u   /* A == A^T exactly: backward reuses the same CSR */
 #define IDG_GRAPH_EXACT_ORDER 2u /* never split a row: every output element is the
                                     sequential CSR-order fmaf chain torch CPU computes */
+#define IDG_GRAPH_NO_BALANCED 4u /* do not build the length-balanced second tile schedule of the dense launches
+                                    (speed only: same bits either way; IDG_BALANCED_TILES=0 in the environment at
+                                    creation does the same for every handle) */
 
 /* CSR arrays are HOST pointers; the handle uploads and owns device copies plus its
  * row-block tile schedule.  split_threshold: rows with more stored entries than this are
@@ -247,8 +250,18 @@ int idg_graph_revalued_copy(const idg_graph* g, const int64_t* d_indptr, const i
 int idg_subgraph_values_f32(int64_t nnz, const int32_t* row_of_entry, const int32_t* col_of_entry,
                             const int32_t* edge_of_entry, const uint32_t* kept_bits, const float* dinv,
                             float* values_out, void* stream);
-/* info[0..7] = n_rows, n_cols, nnz, n_tiles, n_long_rows, n_long_chunks, split_threshold, flags */
+/* info[0..7] = n_rows, n_cols, nnz, n_tiles, n_long_rows, n_long_chunks, split_threshold, flags.  n_tiles: the workgroups
+ * of a dense launch on a cache-resident panel — the tiles of the length-balanced schedule when the handle carries one
+ * (idg_graph_schedule_info reports both schedules). */
 int idg_graph_info(const idg_graph* g, int64_t info[8]);
+/* The handle's two tile schedules: info[0..3] of the one every launch can run on, info[4..7] of the length-balanced one
+ * the dense launches take while the gathered panel is cache resident (all 0 when the handle carries none: switched off,
+ * a panel that is not cache resident at d = 64, EXACT_ORDER rows longer than a tile, a masked / revalued copy).  Each:
+ * tiles, sum of the vrows' rounds (max(1, ceil(entries / 8))), sum over the tiles of 16 x the makespan of the tile's
+ * vrows drawn in list order by 16 lane groups (rounds / that = the share of a resident tile's lane groups that work,
+ * d = 64), device bytes of the schedule (entry list, vrow tables, tiles, split-row table).  A diagnostic: reads the
+ * tables back from the device with blocking copies. */
+int idg_graph_schedule_info(const idg_graph* g, int64_t info[8]);
 /* The split schedule, so a checker can restate the exact summation order.  Define
  *   SEG(entries, S): cut the entry range into consecutive segments of S stored entries, each a
  *   sequential fmaf chain from +0; combine the segment partials p_0, p_1, ... 4-way strided:
