@@ -124,6 +124,14 @@ PROTOTYPES = {
     "idg_mix_nce_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "idg_mix_nce_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp, c_vp, C.c_float,
                                   C.c_float, C.c_float, C.c_float, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "idg_lowrank_project_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "idg_lowrank_project_f32": (C.c_int, [c_vp, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int,
+                                          c_vp, c_vp]),
+    "idg_lowrank_expand_f32": (C.c_int, [c_vp, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int, c_vp,
+                                         C.c_int64, c_vp]),
+    "idg_svd_nce_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "idg_svd_nce_f32": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, C.c_int64, C.c_float,
+                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "idg_kmeans_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "idg_kmeans_assign_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, c_vp, c_vp]),
     "idg_kmeans_update_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, c_vp, c_vp]),

@@ -883,6 +883,64 @@ int idg_mix_nce_f32(const float* panel, int64_t n, int64_t d, int64_t num_users,
                     float* g_panel, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * DEVICE: LightGCL's SVD-view contrastive terms (Cai et al. ICLR'23; models/LightGCL.py:58-120 of the reference) and the two
+ * rank-q products around them.
+ *
+ * The reference forms, per layer l, the view g^l = (A S)(A'^T E'^(l-1)) over ALL rows (A, A' [*, q] the two factor panels
+ * of one truncated SVD, S its singular values) and sums the layers.  By linearity
+ *   G = E^0 + (A S) P,   P = A'^T T',   T = sum_{l < K} E^l = F - E^K     (F the layer sum 0 .. K)
+ * so a step needs two projections to [q, d], and only the batch's rows of G are ever read.
+ *
+ * idg_lowrank_project_f32:  out [q, d] (+)= sum_{r < n} A[a_rows ? a_rows[r] : r, 0:q]^T X[r, 0:d]   (row strides lda, ldx;
+ *   a_rows: DEVICE int64 [n], nullable, rows of A, may repeat: the backward's sum over a batch).  A tall reduction: every
+ *   workgroup owns a fixed run of at least 64 rows (n / 1024 when that is more), each of its row lanes adds its rows
+ *   ascending, the lanes are added in order, and the per-workgroup [q, d] partials meet in the library's one slice reduction.
+ *   n >= 1 (tens of millions: 64-bit row arithmetic), 1 <= q <= 16, 1 <= d <= 256.  ws: idg_lowrank_project_workspace_bytes,
+ *   256-byte aligned (at most 1024 q d floats).
+ * idg_lowrank_expand_f32:   Y[r, 0:d] (+)= scale A[a_rows ? a_rows[r] : r, 0:q] P, r < n, P [q, d] contiguous, k ascending
+ *   (row strides lda, ldy; accumulate != 0 adds into Y).  The backward's dense rank-q update gT += A' dP, and the view rows
+ *   of the differentiable operator.
+ *
+ * idg_svd_nce_f32, one side per call (users: row0 = 0, N = num_users; items: row0 = num_users, N = num_items):
+ *   F_j = final_panel[row0 + j], j < N (row stride d);  ids: DEVICE int64 [B] in [0, N), may repeat (an id outside reads as
+ *   the nearest row of the side);  AS [N, q] contiguous: the side's factor rows times S;  P [q, d] contiguous.
+ *   g_b  = ego_panel[row0 + ids[b]] + AS[ids[b]] P
+ *   s_bj = <g_b, F_j> / tau                                   RAW dot products: nothing is normalised
+ *   loss[0] = (1/B) sum_b log(sum_{j < N} exp(s_bj) + 1e-8)
+ *   loss[1] = (1/B) sum_b clamp(<F_ids[b], g_b> / tau, -5, 5)
+ * loss [2] nullable.  The log-sum-exp carries a true per-row running maximum, online across the table tiles:
+ *   m_b = max_j s_bj,  L_b = m_b + log(sum_j exp(s_bj - m_b) + 1e-8 exp(-m_b))
+ * finite and exact where exp(s) overflows fp32 (s > 88), and still log(1e-8 + ..) where every score is far below zero (a
+ * norm bound in place of the maximum would lose the sum there).
+ * g_final_panel, g_ego_panel [*, d] and dP [q, d] (all or none): with up = upstream (DEVICE [2], NULL = ones) the gradient of
+ * up[0] loss[0] + up[1] loss[1] is ADDED
+ *   into rows [row0, row0 + N) of g_final_panel: sum_b w_bj g_b, w_bj = up[0] / (B tau) softmax-with-guard weight (all N
+ *     rows: the term is dense), and c_b g_b into row row0 + ids[b], c_b = up[1] / (B tau) where -5 <= pos_b <= 5 and
+ *     EXACTLY 0 outside (autograd's clamp); occurrences of one id in batch order;
+ *   into rows row0 + ids[b] of g_ego_panel: gQ_b = sum_j w_bj F_j + c_b F_ids[b], repeated ids summed in batch order;
+ * and dP = sum_b AS[ids[b]]^T gQ_b is STORED (the projection above with the id list).  The panels may coincide: the
+ * additions are made one launch after the other.
+ * The [B, N] matrix is never stored: 128 x 128 score tiles are formed twice (a batch-major pass for the row statistics and
+ * gQ, whose [128, d] accumulator is rescaled in registers when the running maximum moves; a table-major pass for the table
+ * gradient from the stored m_b) on the fp32 matrix cores (v_mfma_f32_32x32x2_f32; operands zero-padded to a multiple of 32
+ * columns: every d <= 256 one path).  A batch below one tile, B <= 127, takes a direct form instead of the two tile passes: its
+ * scores [B, N], row statistics and weights in double (kept in the workspace, 8 B N bytes), one rounding per output — with few
+ * rows nothing averages the fp32 rounding of the scores, which 1 / tau multiplies.  No float atomics, fixed summation orders:
+ * the same bits every run.
+ * Any B >= 1, N >= 1, 1 <= q <= 16.  ws: idg_svd_nce_workspace_bytes, 256-byte aligned (the padded copies, per-chunk
+ * statistics and ordered partial sums: O((N + chunks B) d), chunks <= 64); 0 is returned for sizes that are not built.
+ * ---------------------------------------------------------------------------------- */
+size_t idg_lowrank_project_workspace_bytes(int64_t n, int64_t q, int64_t d);
+int idg_lowrank_project_f32(const float* A, int64_t lda, const int64_t* a_rows, const float* X, int64_t ldx, int64_t n,
+                            int64_t q, int64_t d, float* out, int accumulate, void* ws, void* stream);
+int idg_lowrank_expand_f32(const float* A, int64_t lda, const int64_t* a_rows, const float* P, int64_t n, int64_t q, int64_t d,
+                           float scale, int accumulate, float* Y, int64_t ldy, void* stream);
+size_t idg_svd_nce_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t q);
+int idg_svd_nce_f32(const float* final_panel, const float* ego_panel, int64_t row0, int64_t N, int64_t d, const float* AS,
+                    int64_t q, const float* P, const int64_t* ids, int64_t B, float temperature, float* loss,
+                    const float* upstream, float* g_final_panel, float* g_ego_panel, float* dP, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * DEVICE: Lloyd's k-means, the E-step of NCL (Lin et al. WWW'22; models/NCL.py:66-81 of the reference: faiss.Kmeans on a
  * host copy of each embedding table, then index.search(x, 1) for the final assignment).
  *
