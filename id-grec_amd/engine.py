@@ -153,6 +153,9 @@ class PropagationEngine:
         self.sgl = None        # (temperature, ssl_lambda, sub_graph_1, sub_graph_2): SGL's two edge-dropped views
         self.au = None         # (gamma,): DirectAU — alignment + uniformity over (user, positive) rows replaces BPR; the
         #                        batch's rows are users and positives (negatives ignored: the slots are prepared with neg := pos)
+        self.sccf = None       # (temperature,): SCCF — the in-batch second-order contrastive pair [-up, down] over the same
+        #                        (user, positive) rows replaces BPR, by the same route as `au` (neg := pos, no one-call plan);
+        #                        no regulariser: its rows of self.grad are stored as zeros.  Not together with `au`
         self._views = self._ssl_loss = None
         # one library call per step (StepPlan / idg_step_run_f32) for the plain LightGCN / MFBPR step; IDG_STEP_PLAN=0: the
         # call-by-call chain below (same kernels, same bits)
@@ -210,7 +213,7 @@ class PropagationEngine:
             self.stamp = 0    # order of last hand-out (the ring recycles the oldest)
 
     def _prepare(self, slot, users, pos, neg):
-        if self.au is not None:
+        if self.au is not None or self.sccf is not None:
             neg = pos  # bitmap and scatter plan of users and positives only (idg_align_uniform_f32's plan form)
         main = torch.cuda.current_stream()
         B = users.shape[0]
@@ -300,7 +303,7 @@ class PropagationEngine:
         """The one-call step covers the plain form: deterministic scatter, Adam in the epilogue, no SSL views, no gradient
         exchange, no receptive-field restriction (graphs >= 4 M rows), a tiled width."""
         if not (self._plan_on and self.deterministic and self.fuse_adam and self.ssl is None and self.xssl is None
-                and self.sgl is None and self.au is None and self.exchange is None and not self._compact):
+                and self.sgl is None and self.au is None and self.sccf is None and self.exchange is None and not self._compact):
             return False
         if self.graph is None:
             return self.d % 4 == 0 and self.d <= 1024  # idg_step_create / idg_adam_rows_f32's limits (ADVICE r05)
@@ -363,10 +366,15 @@ class PropagationEngine:
         three = self.ssl is not None or self.xssl is not None or self.sgl is not None or self.au is not None
         loss = (self._loss3 if three else self.loss) if loss_out is None else loss_out
         main = torch.cuda.current_stream()
-        if self.au is not None:
-            neg = pos  # (the slot key and plan of a DirectAU batch: see _prepare)
+        if self.au is not None and self.sccf is not None:
+            raise ValueError("PropagationEngine: au and sccf both replace the BPR call; set one of them")
+        if self.au is not None or self.sccf is not None:
+            neg = pos  # (the slot key and plan of a DirectAU / SCCF batch: see _prepare)
         if self.graph is None:
             self.grad.zero_()
+            if self.sccf is not None and not self.deterministic:
+                ops.sccf_loss_raw(self.params, users, pos, self.U, self.sccf[0], self.grad, loss=loss)
+                return loss
             if self.au is not None and not self.deterministic:
                 ops.align_uniform_raw(self.params, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.grad,
                                       self.grad, loss=loss)
@@ -387,6 +395,8 @@ class PropagationEngine:
             if self.au is not None:
                 ops.align_uniform_raw(self.params, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.grad,
                                       self.grad, loss=loss, plan_ws=slot.ws)
+            elif self.sccf is not None:
+                ops.sccf_loss_raw(self.params, users, pos, self.U, self.sccf[0], self.grad, loss=loss, plan_ws=slot.ws)
             else:
                 ops.bpr_fused_raw(self.params, self.params, users, pos, neg, self.U, self.reg_lambda, self.grad,
                                   self.grad, loss=loss, deterministic=2, ws=slot.ws)
@@ -401,6 +411,8 @@ class PropagationEngine:
             if self.au is not None:
                 ops.align_uniform_raw(self.final, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.g_final,
                                       self.grad, loss=loss)
+            elif self.sccf is not None:
+                ops.sccf_loss_raw(self.final, users, pos, self.U, self.sccf[0], self.g_final, loss=loss)
             else:
                 ops.bpr_fused_raw(self.final, self.params, users, pos, neg, self.U, self.reg_lambda, self.g_final,
                                   self.grad, loss=loss, deterministic=0)
@@ -478,6 +490,10 @@ class PropagationEngine:
             # stored (accumulate=False) — exactly the bitmap's rows, the contract the backward propagation below reads
             ops.align_uniform_raw(self.final, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.g_final,
                                   self.grad, loss=loss[:3], accumulate=False, plan_ws=slot.ws)
+        elif self.sccf is not None:
+            # SCCF: the same place and contract; no term on the ego rows, so its rows of self.grad are stored as zeros
+            ops.sccf_loss_raw(self.final, users, pos, self.U, self.sccf[0], self.g_final, self.grad, loss=loss[:2],
+                              accumulate=False, plan_ws=slot.ws)
         # reached rows of g_final and of the regulariser gradient (self.grad) are STORED and the backward
         # propagation reads flagged rows only: neither panel is ever zero-filled
         # (the bitmap already holds the batch's rows: with TOUCHED_PRESET the scatter stores its rows without writing it, so

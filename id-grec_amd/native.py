@@ -110,6 +110,9 @@ PROTOTYPES = {
     "idg_align_uniform_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "idg_align_uniform_f32": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float,
                                         C.c_float, c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp]),
+    "idg_sccf_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "idg_sccf_loss_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float, c_vp, c_vp, c_vp,
+                                    c_vp, C.c_int, c_vp, c_vp, c_vp]),
     "idg_multinomial_nll_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "idg_multinomial_nll_f32": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                           c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp]),

@@ -772,6 +772,40 @@ int idg_align_uniform_f32(const float* final_panel, const float* ego_panel, int6
                           int accumulate, const void* plan_ws, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * DEVICE: SCCF's in-batch second-order contrastive loss (Wu et al. KDD'24; models/SCCF.py:54-81 of the reference) and its
+ * gradient in one call.  a_i = normalize(final[users[i]]), b_i = normalize(final[num_users + pos[i]]) with
+ * normalize(x) = x / max(||x||, 1e-12), f(s) = exp(s / T) + exp(s^2 / T)  (models/SCCF.py:66-68, 76):
+ *   loss[0] = -(1 / B) sum_i log f(a_i.b_i)                                                   (:70, the list's "-up")
+ *   loss[1] = log(mean over [Nu, Ni] of f(ah_k.bh_l) cu_k ci_l)                               (:72-78, "down")
+ * where ah, bh are the rows of the DISTINCT users and positives of the batch (torch.unique, :60-61) and cu, ci their
+ * multiplicities.  cu_k ci_l counts the occurrences of the pair in B x B, so
+ *   loss[1] = log(sum_{i<B} sum_{j<B} f(a_i.b_j) / (Nu Ni)):
+ * one rectangular Gram problem over the batch rows as they come, and two counts — the run heads of the sorted (row, slot)
+ * plan of idg_bpr_plan_f32(users, pos, pos), user rows < num_users <= item rows.  No unique, no host read-back.  The
+ * reference's list has no regulariser (reg_lambda is read and never used) and ignores the sampled negatives.
+ * With Z = sum sum f every pair's gradient weight is f'(s_ij) / Z, f'(s) = (exp(s / T) + 2 s exp(s^2 / T)) / T: the 128 x 128
+ * score tiles (fp32 matrix cores, operands zero-padded to 32 columns, rows and columns >= B masked) are formed ONCE; the pass
+ * that sums f also forms tile . b-rows and tile^T . a-rows from f', and 1 / Z is applied per slot afterwards.
+ * exp((s - 1) / T) and exp((s^2 - 1) / T) stand for the two exponentials (cosines; 1 / T goes back into the logs).
+ * g_final [n, d], nullable (NULL: the losses only, the same bits as with gradients): d (up[0] loss[0] + up[1] loss[1]) /
+ * d final (upstream: DEVICE [2], NULL = ones), normalize() differentiated through ((g - <g, h> h) / ||x||, the dot product
+ * in double; a row below the floor: g / 1e-12), into the batch's user and positive rows, the occurrences of one row added in
+ * batch order by one wave (in double, rounded once: the slots of a repeated id may nearly cancel).  accumulate != 0: ADDED into those rows; accumulate = 0: the rows of idg_bpr_touch_rows(users,
+ * pos, pos) are STORED, nothing else written.  g_ego [n, d], nullable, distinct from g_final and given only with it: SCCF
+ * has no term on the ego rows — with accumulate = 0 the batch's rows of g_ego are stored as zeros (the engine's "the
+ * bitmap's rows of both panels are stored, neither panel is ever filled" without a memset); otherwise untouched.
+ * plan_ws: NULL, or a BPR workspace (idg_bpr_workspace_bytes(B, d)) holding idg_bpr_plan_f32(users, pos, pos, ...) of THIS
+ * batch; NULL builds the plan in-call, also for the losses alone (the counts come from it).
+ * No float atomics, fixed summation orders: the same bits every run.  1 <= d <= 256, 1 <= B < 2^22, T > 0.
+ * ws: idg_sccf_workspace_bytes, 256-byte aligned: O(B d) plus the per-tile partial gradient rows, ceil(B / 128) slices of
+ * [2, B, d] (16 MiB at B = 2048, d = 64); 0 is returned for sizes not built.
+ * ---------------------------------------------------------------------------------- */
+size_t idg_sccf_workspace_bytes(int64_t B, int64_t d);
+int idg_sccf_loss_f32(const float* final_panel, int64_t n, int64_t d, const int64_t* users, const int64_t* pos, int64_t B,
+                      int64_t num_users, float temperature, float* loss /*[2]*/, const float* upstream /*DEVICE [2], NULL = ones*/,
+                      float* g_final, float* g_ego, int accumulate, const void* plan_ws, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * DEVICE: CVGA's decoder loss and VAE head (Zhang et al. TOIS'23; models/CVGA.py:40-85 and
  * utility/utility_function/losses.py:53-56 of the reference), forward and backward.
  *
