@@ -1291,12 +1291,14 @@ __global__ __launch_bounds__(64) void spmm_xl_kernel(const int32_t* __restrict__
                                                      const int32_t* __restrict__ vtgt,
                                                      const ColVal* __restrict__ cv,
                                                      const float* __restrict__ X, int64_t ldx,
-                                                     Epilogue ep, const uint32_t* __restrict__ x_mask) {
+                                                     Epilogue ep, const uint32_t* __restrict__ x_mask,
+                                                     const uint32_t* __restrict__ out_mask) {
   const int v = xl[blockIdx.x];
   const int l = threadIdx.x;
   if (l >= LPR) return;
   const int64_t s = vptr[v], e = vptr[v + 1];
   const int tgt = vtgt[v];
+  if (out_mask && !mask_bit(out_mask, tgt)) return;  // row not requested (block-uniform)
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const int off = (b * LPR + l) * 4;
@@ -1678,7 +1680,7 @@ int launch_fast(const idg_graph* g, const float* X, int64_t ldx, float* partials
   }
   if (g->n_xl > 0)
     hipLaunchKernelGGL((spmm_xl_kernel<LPR, NB>), dim3((unsigned)g->n_xl), dim3(64), 0, st, g->d_xl, g->d_vptr,
-                       g->d_vtgt, g->d_cv, X, ldx, ep, x_mask);
+                       g->d_vtgt, g->d_cv, X, ldx, ep, x_mask, out_mask);
   if (g->n_long > 0 && !fused_fix) {
     hipLaunchKernelGGL((spmm_fixup_kernel<LPR, NB>), dim3((unsigned)g->n_long), dim3(FIX_WAYS * LPR), 0, st,
                        g->d_long, (int)g->n_long, partials, d, ep, out_mask);

@@ -378,8 +378,9 @@ int idg_propagate_views_f32(const idg_graph* g, const float* E0, int K, int64_t 
 size_t idg_propagate_workspace_bytes(const idg_graph* g, int64_t d);
 /* out_rows (nullable): bitmap of the rows of `out` the caller will read.  The LAST layer's product
  * feeds nothing but the mean, so with a bitmap it is evaluated for the flagged rows only (bit-
- * identical values there; every other row of `out` is left untouched).  A training step reads the
- * mean at the <= 3B rows of its batch: idg_bpr_touch_rows builds that bitmap from the indices. */
+ * identical values there; for K <= 3 every other row of `out` is left untouched, for K > 3 `out`
+ * carries the running sum and its other rows hold the sum of the earlier layers).  A training step
+ * reads the mean at the <= 3B rows of its batch: idg_bpr_touch_rows builds that bitmap from the indices. */
 int idg_propagate_mean_f32(const idg_graph* g, const float* E0, float* out,
                            const uint32_t* out_rows, int K, int include_layer0, int64_t d, void* ws,
                            void* stream);
