@@ -156,6 +156,11 @@ class PropagationEngine:
         self.sccf = None       # (temperature,): SCCF — the in-batch second-order contrastive pair [-up, down] over the same
         #                        (user, positive) rows replaces BPR, by the same route as `au` (neg := pos, no one-call plan);
         #                        no regulariser: its rows of self.grad are stored as zeros.  Not together with `au`
+        self.na = None         # (temperature, weight, margin_or_None, with_bpr): LightCCF / LightCSCF — the neighbour-aggregation
+        #                        loss over the (user, positive) rows of the final panel (idg_na_nce_f32), ADDED to the rows the
+        #                        step's first call stored.  with_bpr=True: that call is BPR as it stands, the loss gets a third
+        #                        entry [bpr, reg, na]; False (LightCSCF on LightGCN): the regulariser alone (idg_reg_rows_f32),
+        #                        two losses [reg, na].  Not together with `au` or `sccf`; no one-call plan
         self._views = self._ssl_loss = None
         # one library call per step (StepPlan / idg_step_run_f32) for the plain LightGCN / MFBPR step; IDG_STEP_PLAN=0: the
         # call-by-call chain below (same kernels, same bits)
@@ -303,7 +308,8 @@ class PropagationEngine:
         """The one-call step covers the plain form: deterministic scatter, Adam in the epilogue, no SSL views, no gradient
         exchange, no receptive-field restriction (graphs >= 4 M rows), a tiled width."""
         if not (self._plan_on and self.deterministic and self.fuse_adam and self.ssl is None and self.xssl is None
-                and self.sgl is None and self.au is None and self.sccf is None and self.exchange is None and not self._compact):
+                and self.sgl is None and self.au is None and self.sccf is None and self.na is None and self.exchange is None
+                and not self._compact):
             return False
         if self.graph is None:
             return self.d % 4 == 0 and self.d <= 1024  # idg_step_create / idg_adam_rows_f32's limits (ADVICE r05)
@@ -355,6 +361,16 @@ class PropagationEngine:
     def touched(self, value):
         self._touched = value
 
+    def _na_call(self, final, users, pos, g_final, loss, plan_ws):
+        """With `na` set: the neighbour-aggregation loss into the entry behind the step's first call's, its gradient ADDED
+        into g_final's rows of the batch's users and positives."""
+        if self.na is None:
+            return
+        temperature, weight, margin, with_bpr = self.na
+        k = 2 if with_bpr else 1
+        ops.na_nce_loss_raw(final, users, pos, self.U, temperature, margin, weight, g_final, loss=loss[k:k + 1],
+                            accumulate=True, plan_ws=plan_ws)
+
     # ---- forward + backward: losses [bpr, reg_lambda*reg] and d(sum)/dE0 into self.grad
     @torch.no_grad()
     def loss_and_grad(self, users, pos, neg, loss_out=None, _adam_step=0):
@@ -363,11 +379,15 @@ class PropagationEngine:
         With self.ssl set (SimGCL): two noise-perturbed encoder passes next to the clean one, InfoNCE between
         them over the batch's unique users / positive items, its gradients added (times ssl_lambda) to the BPR
         gradient before the ONE backward propagation all three passes share; loss gets a third entry."""
-        three = self.ssl is not None or self.xssl is not None or self.sgl is not None or self.au is not None
+        three = (self.ssl is not None or self.xssl is not None or self.sgl is not None or self.au is not None
+                 or (self.na is not None and self.na[3]))
         loss = (self._loss3 if three else self.loss) if loss_out is None else loss_out
         main = torch.cuda.current_stream()
         if self.au is not None and self.sccf is not None:
             raise ValueError("PropagationEngine: au and sccf both replace the BPR call; set one of them")
+        if self.na is not None and (self.au is not None or self.sccf is not None):
+            raise ValueError("PropagationEngine: na joins the BPR call (or the regulariser alone), which au and sccf replace; "
+                             "set one of them")
         if self.au is not None or self.sccf is not None:
             neg = pos  # (the slot key and plan of a DirectAU / SCCF batch: see _prepare)
         if self.graph is None:
@@ -380,8 +400,12 @@ class PropagationEngine:
                                       self.grad, loss=loss)
                 return loss
             if not self.deterministic:
-                ops.bpr_fused_raw(self.params, self.params, users, pos, neg, self.U, self.reg_lambda, self.grad,
-                                  self.grad, loss=loss, deterministic=0)
+                if self.na is not None and not self.na[3]:
+                    ops.reg_rows_raw(self.params, users, pos, neg, self.U, self.reg_lambda, g_ego=self.grad, loss=loss[0:1])
+                else:
+                    ops.bpr_fused_raw(self.params, self.params, users, pos, neg, self.U, self.reg_lambda, self.grad,
+                                      self.grad, loss=loss[:2], deterministic=0)
+                self._na_call(self.params, users, pos, self.grad, loss, None)
                 return loss
             # the sorted scatter plan depends on the indices only: prepared on the side stream (by prefetch() during the
             # previous step, or right now) — in-call it is half of an MFBPR step
@@ -397,9 +421,13 @@ class PropagationEngine:
                                       self.grad, loss=loss, plan_ws=slot.ws)
             elif self.sccf is not None:
                 ops.sccf_loss_raw(self.params, users, pos, self.U, self.sccf[0], self.grad, loss=loss, plan_ws=slot.ws)
+            elif self.na is not None and not self.na[3]:
+                ops.reg_rows_raw(self.params, users, pos, neg, self.U, self.reg_lambda, g_ego=self.grad, loss=loss[0:1],
+                                 plan_ws=slot.ws)
             else:
                 ops.bpr_fused_raw(self.params, self.params, users, pos, neg, self.U, self.reg_lambda, self.grad,
-                                  self.grad, loss=loss, deterministic=2, ws=slot.ws)
+                                  self.grad, loss=loss[:2], deterministic=2, ws=slot.ws)
+            self._na_call(self.params, users, pos, self.grad, loss, slot.ws)
             slot.free = slot.free_ev
             slot.free.record(main.cuda_stream)
             self._final_version = -1
@@ -413,9 +441,12 @@ class PropagationEngine:
                                       self.grad, loss=loss)
             elif self.sccf is not None:
                 ops.sccf_loss_raw(self.final, users, pos, self.U, self.sccf[0], self.g_final, loss=loss)
+            elif self.na is not None and not self.na[3]:
+                ops.reg_rows_raw(self.params, users, pos, neg, self.U, self.reg_lambda, g_ego=self.grad, loss=loss[0:1])
             else:
                 ops.bpr_fused_raw(self.final, self.params, users, pos, neg, self.U, self.reg_lambda, self.g_final,
-                                  self.grad, loss=loss, deterministic=0)
+                                  self.grad, loss=loss[:2], deterministic=0)
+            self._na_call(self.final, users, pos, self.g_final, loss, None)
             self.graph.propagate_mean_bwd_raw(self.g_final, self.K, self.inc, out=self.grad, accumulate=True)
             self._final_version = -1
             return loss
@@ -498,10 +529,18 @@ class PropagationEngine:
         # propagation reads flagged rows only: neither panel is ever zero-filled
         # (the bitmap already holds the batch's rows: with TOUCHED_PRESET the scatter stores its rows without writing it, so
         #  the lists registered for it — the compacted inputs of the first backward product — stay valid)
+        elif self.na is not None and not self.na[3]:
+            # LightCSCF on LightGCN: no BPR term — the regulariser's rows of self.grad are STORED, and zeros to the same rows
+            # of g_final (users, positives and negatives: the bitmap's rows), before the call below ADDS its rows
+            ops.reg_rows_raw(self.params, users, pos, neg, self.U, self.reg_lambda, g_ego=self.grad, g_final=self.g_final,
+                             loss=loss[0:1], plan_ws=slot.ws)
         else:
             ops.bpr_fused_raw(self.final, self.params, users, pos, neg, self.U, self.reg_lambda, self.g_final,
                               self.grad, loss=loss[:2], deterministic=2 | native.IDG_BPR_TOUCHED_PRESET, touched=slot.bitmap,
                               ws=slot.ws)
+        # LightCCF / LightCSCF: d(weight * na) / d final joins in g_final's (stored) rows — users and positives are a subset
+        # of the bitmap — where SimGCL's InfoNCE gradient joins below
+        self._na_call(self.final, users, pos, self.g_final, loss, slot.ws)
         if self.ssl is not None:
             # d(ssl_lambda * InfoNCE)/d view_1 + d(...)/d view_2 join the BPR gradient in g_final's (stored) rows
             ops.infonce_pair_raw(self._views[0], self._views[1], users, pos, self.U, temperature, g1=self.g_final,

@@ -113,6 +113,11 @@ PROTOTYPES = {
     "idg_sccf_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "idg_sccf_loss_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float, c_vp, c_vp, c_vp,
                                     c_vp, C.c_int, c_vp, c_vp, c_vp]),
+    "idg_na_nce_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "idg_na_nce_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float,
+                                 c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp]),
+    "idg_reg_rows_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, c_vp, c_vp, c_vp, C.c_int64, C.c_int64, C.c_float, c_vp, c_vp,
+                                   c_vp, c_vp, c_vp, c_vp]),
     "idg_multinomial_nll_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "idg_multinomial_nll_f32": (C.c_int, [c_vp, c_vp, c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                           c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp]),

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define IDG_VERSION 142 /* 0.5.3 (added since, no entry point changed, so the number stays): idg_table_nce_f32 / idg_table_nce_workspace_bytes (CGCL's full-table contrastive loss: every batch row against a whole normalised embedding table, forward and backward); 0.5.3: idg_multinomial_nll_f32 / idg_multinomial_nll_workspace_bytes (CVGA's decoder: linear + log-softmax + multinomial NLL over the catalogue, forward and backward), idg_vae_head_fwd_f32 / idg_vae_head_bwd_f32 / idg_vae_head_workspace_bytes (its VAE head); 0.5.2: idg_align_uniform_f32 / idg_align_uniform_workspace_bytes (DirectAU's alignment + uniformity loss); 0.5.1: idg_pack24_f32 / idg_unpack24_f32 / idg_reduce24_f32 / idg_alltoall_f32 (24-bit panel exchange, rank-ordered sum), idg_score_topk_candidate_counts, idg_score_topk_option (the top-K knobs: environment read once), idg_score_topk_info fills info[8], form 3's whole-call fall-back; idg_step_run_f32 takes next_ids_token; idg_step_synchronize also drains the side stream's preparations; 0.5.0: idg_step_* (one library call per training step), idg_adam_rows_f32; 0.4.4: IDG_ADAM_DISCARD_GRAD; 0.4.3: idg_event_synchronize; 0.4.2: idg_infonce_plan / IDG_SSL_PLANNED / idg_infonce_cross_ex_f32 (InfoNCE id lists a batch ahead); 0.4.1: idg_ngcf_layer_fwd_f32 / idg_ngcf_layer_bwd_f32 (one kernel per NGCF layer and direction); 0.4.0: idg_rows_layer_mean_n_f32 (any number of layers), idg_flags_compact_f32 (the touched-item
+#define IDG_VERSION 142 /* 0.5.3 (added since, no entry point changed, so the number stays): idg_na_nce_f32 / idg_na_nce_workspace_bytes / idg_reg_rows_f32 (LightCCF's and LightCSCF's neighbour-aggregation loss, and the regulariser without a BPR call); idg_table_nce_f32 / idg_table_nce_workspace_bytes (CGCL's full-table contrastive loss: every batch row against a whole normalised embedding table, forward and backward); 0.5.3: idg_multinomial_nll_f32 / idg_multinomial_nll_workspace_bytes (CVGA's decoder: linear + log-softmax + multinomial NLL over the catalogue, forward and backward), idg_vae_head_fwd_f32 / idg_vae_head_bwd_f32 / idg_vae_head_workspace_bytes (its VAE head); 0.5.2: idg_align_uniform_f32 / idg_align_uniform_workspace_bytes (DirectAU's alignment + uniformity loss); 0.5.1: idg_pack24_f32 / idg_unpack24_f32 / idg_reduce24_f32 / idg_alltoall_f32 (24-bit panel exchange, rank-ordered sum), idg_score_topk_candidate_counts, idg_score_topk_option (the top-K knobs: environment read once), idg_score_topk_info fills info[8], form 3's whole-call fall-back; idg_step_run_f32 takes next_ids_token; idg_step_synchronize also drains the side stream's preparations; 0.5.0: idg_step_* (one library call per training step), idg_adam_rows_f32; 0.4.4: IDG_ADAM_DISCARD_GRAD; 0.4.3: idg_event_synchronize; 0.4.2: idg_infonce_plan / IDG_SSL_PLANNED / idg_infonce_cross_ex_f32 (InfoNCE id lists a batch ahead); 0.4.1: idg_ngcf_layer_fwd_f32 / idg_ngcf_layer_bwd_f32 (one kernel per NGCF layer and direction); 0.4.0: idg_rows_layer_mean_n_f32 (any number of layers), idg_flags_compact_f32 (the touched-item
                            agreement without a host read-back), idg_shard_prepare validates its geometry.
                            133 / 0.3.0: process-wide live-unit registry + idg_graph_live_units_check; idg_spmm_epi_f32 (every
                            epilogue option; out_rows and x_rows combined); round-3 sharded step: idg_rows_gather2 / _scatter /
@@ -805,6 +805,53 @@ size_t idg_sccf_workspace_bytes(int64_t B, int64_t d);
 int idg_sccf_loss_f32(const float* final_panel, int64_t n, int64_t d, const int64_t* users, const int64_t* pos, int64_t B,
                       int64_t num_users, float temperature, float* loss /*[2]*/, const float* upstream /*DEVICE [2], NULL = ones*/,
                       float* g_final, float* g_ego, int accumulate, const void* plan_ws, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * DEVICE: the neighbour-aggregation loss of LightCCF (Zhang et al. SIGIR'25; models/LightCCF.py:81-94 of the reference) and
+ * LightCSCF (models/LightCSCF.py:93-104) and its gradient in one call.  a_i = normalize(final[users[i]]),
+ * b_i = normalize(final[num_users + pos[i]]) with normalize(x) = x / max(||x||, 1e-12), p_i = a_i.b_i:
+ *   total_score[i, j] = a_i.b_j + a_i.a_j = a_i.c_j,  c_j = a_j + b_j        (the SUM of the two matrices is inside exp)
+ *   T_i = sum_j f(a_i.c_j)  (every j, the diagonal included),   r_i = f(p_i) / T_i
+ *   loss[0] = grad_scale (1 / B) sum_i -log(r_i + 1e-5)                                      (the reference's `10e-6`)
+ *   margin < 0 (LightCCF):  f(s) = exp(s / T);   0 <= margin <= 2 (LightCSCF):  f(s) = exp(s / T) + exp(relu(s - margin) / T)
+ * grad_scale carries ssl_lambda / lambda_gamma.  One rectangular Gram problem A C^T over the batch rows as they come, on
+ * 64 x 64 score tiles (operands zero-padded to 32 columns, rows and columns >= B masked), never stored as a [B, B] matrix.
+ * The diagonal makes r_i <= exp(-1 / T), the order of the 1e-5 at small T, so row i's gradient carries
+ * w_i = r_i / (r_i + 1e-5) and needs T_i complete: the tiles are formed again after a row-sum pass (each partial written by
+ * one workgroup, combined in a fixed order), with P_ij = w_i f'(s_ij) / (T_i B), for P . C and for P^T . A.
+ * G_c[j] = sum_i P_ij a_i reaches both a_j and b_j; a_i also takes sum_j P_ij c_j and, with b_i, the positive term.  Every
+ * exponential carries the fixed shift -2 / T (scores <= 2), which cancels in r_i and in every gradient weight; T >= 0.01.
+ * The whole term runs in DOUBLE — normalised rows, scores and both products on v_mfma_f64_16x16x4_f64, exponentials, sums:
+ * at a low temperature the diagonal and the columns repeating a row's user hold nearly all of T_i, and the gradient is the rest
+ * of parts that cancel, 1e2 ... 1e5 times smaller than they are; float32 operands or tiles leave it wrong by up to percents
+ * (csrc/idg_nance.hip).  The inputs and the gradient panel stay float32.
+ * g_final [n, d], nullable (NULL: the loss only, the same bits as with gradients): upstream * d loss[0] / d final (upstream:
+ * DEVICE [1], NULL = 1), normalize() differentiated through ((g - <g, h> h) / ||x||, in double; a row below the floor:
+ * g / 1e-12), into the batch's user and positive rows, the occurrences of one row added in batch order by one wave (in
+ * double, rounded once).  accumulate != 0: ADDED into those rows; accumulate = 0: every row of the plan is STORED (a row
+ * that only third slots of the plan name: zeros), nothing else written.
+ * plan_ws: NULL, or a BPR workspace (idg_bpr_workspace_bytes(B, d)) holding idg_bpr_plan_f32(users, pos, x, ...) of THIS batch
+ * (x = the negatives or the positives: third slots carry no term); NULL builds the plan of (users, pos, pos) in-call when a
+ * gradient is asked for.  No float atomics, fixed summation orders: the same bits every run.  1 <= d <= 256, 1 <= B < 2^22.
+ * ws: idg_na_nce_workspace_bytes, 256-byte aligned: O(B d) doubles, the partial products of at most 8 splits of the tile walk
+ * included (43 MiB at B = 4096, d = 64); 0 is returned for sizes not built.
+ *
+ * idg_reg_rows_f32: the regulariser alone, for a step without a BPR call to carry it (LightCSCF on LightGCN,
+ * models/LightCSCF.py:82-89): loss[0] = reg_lambda (1/2) (sum ||e_u||^2 + sum ||e_p||^2 + sum ||e_n||^2) / B over the ego rows
+ * of users, positives AND negatives, duplicates counted.  Over the sorted plan of idg_bpr_plan_f32(users, pos, neg, ...)
+ * (plan_ws; NULL builds it in-call from the three lists): g_ego (nullable) has the gradient rows STORED (occurrences added
+ * in batch order in double, rounded once), g_final (nullable, distinct from g_ego) has zeros STORED to the same rows, so every
+ * row of the batch's bitmap is defined before idg_na_nce_f32 ADDS the users' and positives' rows.  ws: a buffer of
+ * idg_na_nce_workspace_bytes bytes for this B and d (it may be the one the idg_na_nce_f32 call that follows uses).
+ * ---------------------------------------------------------------------------------- */
+size_t idg_na_nce_workspace_bytes(int64_t B, int64_t d);
+int idg_na_nce_f32(const float* final_panel, int64_t n, int64_t d, const int64_t* users, const int64_t* pos, int64_t B,
+                   int64_t num_users, float temperature, float margin /* < 0: none */, float grad_scale, float* loss /*[1]*/,
+                   const float* upstream /*DEVICE [1], NULL = 1*/, float* g_final, int accumulate, const void* plan_ws, void* ws,
+                   void* stream);
+int idg_reg_rows_f32(const float* ego_panel, int64_t n, int64_t d, const int64_t* users, const int64_t* pos, const int64_t* neg,
+                     int64_t B, int64_t num_users, float reg_lambda, float* loss /*[1]*/, float* g_ego, float* g_final,
+                     const void* plan_ws, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * DEVICE: CVGA's decoder loss and VAE head (Zhang et al. TOIS'23; models/CVGA.py:40-85 and

@@ -1,0 +1,198 @@
+"""LightCCF (Zhang et al., SIGIR'25) and LightCSCF, its margin variant, stated once more in plain torch with autograd and (by
+default) float64: what tests/test_gpu_na.py holds idgrec_amd/csrc/idg_nance.hip, ops.na_nce_loss, ops.reg_rows_raw, the
+engine hook and the two plugins against, and what tests/test_na_host.py pins to the reference's own numbers
+(tests/golden/na_small.npz on graph_small.npz's graph) without a GPU.  Nothing of the library, and nothing of the reference, is
+imported here.
+
+    X = E0 (encoder MF)  or  mean_{k=0..K} A^k E0 (any other encoder)
+    a_i = normalize(X[users[i]]),  b_i = normalize(X[U + pos[i]]),  p_i = a_i.b_i
+    na = mean_i -log( f(p_i) / sum_j f(a_i.b_j + a_i.a_j) + 1e-5 )
+    LightCCF: f(s) = exp(s / T);   LightCSCF: f(s) = exp(s / T) + exp(relu(s - m) / T)
+    losses = [bpr, reg_lambda * reg, weight * na]     (LightCSCF on a non-MF encoder: [reg_lambda * reg, weight * na])
+
+The term in two forms: `literal` — two matmuls added, then exp, as the reference spells it — and `collapsed` — the one
+product A (A + B)^T the kernel forms.  The float32 evaluation of the LITERAL form is the yardstick of the GPU tests: how far
+a correct float32 evaluation sits from the float64 statement."""
+import torch
+import torch.nn.functional as F
+
+from tests.egcf_ref64 import adam64, dense_operator, deterministic, errors  # noqa: F401
+
+KINK_GAP = 1e-5  # LightCSCF's relu(s - m): no score of a test case within this of m (float32 and float64 would branch apart)
+
+
+def _hat(x):
+    return F.normalize(x, dim=-1)
+
+
+def _f(s, t, margin):
+    out = (s / t).exp()
+    if margin is not None:
+        out = out + (torch.relu(s - margin) / t).exp()
+    return out
+
+
+def _unit_scores(a, b, collapsed=False):
+    p = (a * b).sum(dim=-1)
+    total = a @ (a + b).T if collapsed else a @ b.T + a @ a.T
+    return p, total
+
+
+def scores(a_rows, b_rows, collapsed=False):
+    """(p [B], total_score [B, B]) of the gathered rows."""
+    return _unit_scores(_hat(a_rows), _hat(b_rows), collapsed)
+
+
+def _na_unit(a, b, t, margin, collapsed=False):
+    p, total = _unit_scores(a, b, collapsed)
+    return (-torch.log(_f(p, t, margin) / _f(total, t, margin).sum(dim=1) + 10e-6)).mean()
+
+
+def na64(a_rows, b_rows, t, margin=None, collapsed=False):
+    """mean_i -log(f(p_i) / sum_j f(total_score[i, j]) + 10e-6) of the gathered rows (any dtype; differentiable)."""
+    return _na_unit(_hat(a_rows), _hat(b_rows), t, margin, collapsed)
+
+
+def grad_scale(panel, U, users, pos, t, margin, g64, weight=1.0, upstream=None):
+    """What a gradient error of a case is divided by: the largest entry of the float64 gradient — except at B = 1.  There
+    LightCCF's term is the constant -log(exp(-1 / T) + 1e-5) (the one score is 1 + p, the ratio exp(-1 / T) whatever the rows)
+    and LightCSCF's depends on the rows through the margin alone: the gradient is zero, or the small rest of two parts that
+    cancel — d loss / d a_hat is a multiple of a_hat, which normalize()'s projection removes — and what ANY float evaluation
+    returns for it is the rounding of those parts.  So at B = 1 the scale is that of the parts: the largest entry of
+    d loss / d (a_hat, b_hat) divided by the rows' norms, in float64 (never smaller than the gradient's own largest entry)."""
+    own = float(g64.abs().max())
+    if users.shape[0] != 1:
+        return own
+    X = panel.detach().double().cpu()
+    xa, xb = X[users.long().cpu()], X[U + pos.long().cpu()]
+    a, b = _hat(xa).requires_grad_(True), _hat(xb).requires_grad_(True)
+    ga, gb = torch.autograd.grad((1.0 if upstream is None else upstream) * weight * _na_unit(a, b, t, margin), (a, b))
+    parts = max(float((ga / xa.norm(dim=1, keepdim=True)).abs().max()), float((gb / xb.norm(dim=1, keepdim=True)).abs().max()))
+    return max(own, parts)
+
+
+def kink_distance(panel, U, users, pos, margin):
+    """The smallest |score - m| over A C^T and the positives, in float64: every LightCSCF case asserts it above KINK_GAP."""
+    X = panel.detach().double().cpu()
+    p, total = scores(X[users.long().cpu()], X[U + pos.long().cpu()], collapsed=True)
+    return float(torch.minimum((total - margin).abs().min(), (p - margin).abs().min()))
+
+
+def panel_terms(panel, U, users, pos, t, margin=None, weight=1.0, dtype=torch.float64, upstream=None, collapsed=False):
+    """(loss = weight * na, upstream * d loss / d panel) on the rows of an [n, d] panel."""
+    X = panel.detach().to(dtype).clone().requires_grad_(True)
+    users, pos = users.long(), pos.long()
+    with deterministic():
+        loss = weight * na64(X[users], X[U + pos], t, margin, collapsed)
+        (g,) = torch.autograd.grad((1.0 if upstream is None else upstream) * loss, X)
+    return loss.detach(), g
+
+
+def reg64(E0, U, users, pos, neg, reg_lambda, dtype=torch.float64):
+    """(reg_lambda * get_reg_loss(E0[users], E0[U + pos], E0[U + neg]), its gradient w.r.t. E0)."""
+    E = E0.detach().to(dtype).clone().requires_grad_(True)
+    with deterministic():
+        loss = reg_lambda * sum(0.5 * blk.norm(2).pow(2) / float(blk.shape[0]) for blk in (E[users.long()], E[U + pos.long()], E[U + neg.long()]))
+        (g,) = torch.autograd.grad(loss, E)
+    return loss.detach(), g
+
+
+def propagate64(A, E0, K):
+    x, total = E0, E0
+    for _ in range(K):
+        x = A @ x
+        total = total + x
+    return total / (K + 1)
+
+
+def step64(A, E0, users, pos, neg, layers, t, num_users, reg_lambda, weight, margin=None, with_bpr=True, dtype=torch.float64,
+           collapsed=False):
+    """The forward and backward of LightCCF (margin None) / LightCSCF.  A: the dense [n, n] operator, or None for the MF encoder
+    (layers is then ignored); E0: the [n, d] ego panel, users first; with_bpr=False: LightCSCF on a non-MF encoder, whose list
+    has no BPR entry.  Returns (losses [3] or [2], d sum(losses) / d E0, X)."""
+    U = int(num_users)
+    E0 = E0.detach().to(dtype).clone().requires_grad_(True)
+    users, pos, neg = users.long(), pos.long(), neg.long()
+    with deterministic():
+        X = E0 if A is None else propagate64(A.to(dtype), E0, layers)
+        ue, pe, ne = X[users], X[U + pos], X[U + neg]
+        reg = reg_lambda * sum(0.5 * blk.norm(2).pow(2) / float(blk.shape[0]) for blk in (E0[users], E0[U + pos], E0[U + neg]))
+        na = weight * na64(ue, pe, t, margin, collapsed)
+        ll = [reg, na]
+        if with_bpr:
+            x = (ue * pe).sum(dim=1) - (ue * ne).sum(dim=1)
+            ll.insert(0, torch.mean(-torch.log(torch.sigmoid(x) + 10e-8)))
+        (g,) = torch.autograd.grad(sum(ll), E0)
+    return torch.stack(ll).detach(), g, X.detach()
+
+
+def case_inputs(B, d, seed, U=45, I=61, device="cpu", form="random"):
+    """The inputs of one case of the GPU tests' grid, drawn on the CPU (the same numbers on either side): the panel
+    [U + I, d] and the id lists.  form: `random` (B >= U or I repeats ids), `distinct` (U = I = B rows, a permutation
+    each), `one_user` (one user B times), `zero_rows` (`random` with two panel rows zeroed)."""
+    gen = torch.Generator().manual_seed(seed)
+    if form == "distinct":
+        U = I = B
+    panel = torch.randn(U + I, d, generator=gen, dtype=torch.float32) * 0.3
+    if form == "distinct":
+        users, pos = torch.randperm(B, generator=gen), torch.randperm(B, generator=gen)
+    else:
+        users = torch.randint(0, U, (B,), generator=gen)
+        pos = torch.randint(0, I, (B,), generator=gen)
+        if form == "one_user":
+            users = torch.full((B,), int(users[0]), dtype=torch.int64)
+        if form == "zero_rows":  # a zero panel row as user and as positive (zero_rows_of names them)
+            panel[int(users[2])] = 0
+            panel[U + int(pos[5])] = 0
+    return panel.to(device), users.to(device), pos.to(device), U
+
+
+GRID_B = (1, 96, 127, 128, 129, 257)
+GRID_D = (48, 64, 100, 256)
+GRID_T = (0.1, 1.0)
+MARGIN = 0.7
+GRID_M = (None, MARGIN)  # both forms of f
+EXTRA = (129, 64, 0.05)  # the one extra case at the low end of the temperature range (both forms of f)
+
+
+def grid_seed(B, d, t):
+    """Chosen on the CPU so that every LightCSCF case of the grid keeps KINK_GAP from the margin (tests/test_na_host.py
+    asserts it for every case).  One seed was moved: B = 129, d = 48, T = 0.1 drew a score 3.6e-6 from the margin."""
+    return B * 1000 + d + (7 if t == 1.0 else 0) + (100000 if (B, d, t) == (129, 48, 0.1) else 0)
+
+
+def grid_upstream(B):
+    """The incoming gradient of a grid case: -1.3 at B = 1 and at B = 129, None (= 1) elsewhere."""
+    return -1.3 if B in (1, 129) else None
+
+
+def zero_rows_of(users, pos, U):
+    return (int(users[2]), U + int(pos[5]))
+
+
+# the cases that ride on a few sizes of the grid: (form, B, d, T, margin, seed)
+RIDERS = tuple((form, B, d, t, m, 31 * B + d) for form in ("distinct", "one_user")
+               for B, d, t, m in ((96, 64, 0.1, None), (129, 48, 1.0, MARGIN), (257, 100, 0.1, MARGIN))) \
+    + tuple(("zero_rows", B, d, t, m, 17 * B + d) for B, d, t, m in ((129, 64, 0.1, MARGIN), (96, 100, 1.0, None))) \
+    + tuple(("random", B, d, t, m, 13 * B + d) for B, d, t, m in ((127, 64, 0.1, None), (257, 48, 1.0, MARGIN)))
+
+
+def all_cases():
+    """Every (form, B, d, T, margin, seed) the GPU tests and the float32 yardstick run over: the grid, the extra case, the
+    riders."""
+    out = [("random", B, d, t, m, grid_seed(B, d, t)) for B in GRID_B for d in GRID_D for t in GRID_T for m in GRID_M]
+    out += [("random",) + EXTRA + (m, grid_seed(*EXTRA)) for m in GRID_M]
+    return out + list(RIDERS)
+
+
+# the four settings of the fixture: (model, encoder)
+SETTINGS = {"ccf_mf": ("LightCCF", "MF"), "ccf_gcn": ("LightCCF", "LightGCN"), "cscf_mf": ("LightCSCF", "MF"),
+            "cscf_gcn": ("LightCSCF", "LightGCN")}
+
+
+def setting_terms(tag, hyper):
+    """(reg_lambda, weight, margin, with_bpr, temperature, layers, learn_rate) of a fixture setting from its `_hyper` row
+    [temperature, GCN_layer, learn_rate, reg, weight, margin (-1: none)]."""
+    t, layers, lr, reg, weight, margin = [float(x) for x in hyper]
+    model, enc = SETTINGS[tag]
+    return reg, weight, (None if margin < 0 else margin), not (model == "LightCSCF" and enc != "MF"), t, int(layers), lr
