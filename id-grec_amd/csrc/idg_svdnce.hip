@@ -17,7 +17,8 @@
 //   gQ_b = sum_j w_bj F_j + c_b F_id_b,   gF_j += sum_b w_bj g_b,   gF_id_b += c_b g_b,   dP = sum_b AS[id_b]^T gQ_b
 //
 // Layout, as idg_tnce.hip: the operands are copied once into the workspace, rows padded with zero rows to a multiple of
-// 128 and columns with zero columns to a multiple of 32; every product is v_mfma_f32_32x32x2_f32.
+// 128 and columns with zero columns to a multiple of 32; every product is v_mfma_f32_32x32x2_f32, and a score's features are
+// summed 32 at a time (score_tile_chunked below).
 //   prep    one wave per row: the padded table copy; the query rows g_b (the rank-q expansion, k ascending).
 //   sums    grid (batch tile, table chunk): a workgroup owns 128 query rows and walks the 128-row table tiles of its
 //           chunk.  Per tile: the raw scores into the 128 x 128 LDS tile (-inf past row N), the row maxima, the new running
@@ -275,6 +276,72 @@ __global__ __launch_bounds__(BLOCK) void svd_prep_kernel(const float* __restrict
   }
 }
 
+// S = X Y^T as tile128::score_tile_128 lays it out, with the features added 32 at a time: each 32-column chunk is summed in
+// an accumulator of its own (ascending, exact fp32 products) and the chunks' sums are added in ascending order.  The raw
+// scores here are divided by tau inside an exponent, so a weight carries 1 / tau times a score's rounding; one chain of d
+// terms left g_ego 3.7e-6 of its largest entry from float64 at d = 224, tau = 0.2 (plain float32 torch: 1.6e-6), the
+// chains of 32 leave about a third of that.  One chunk (d <= 32) is the shared tile itself, bit for bit.  Ends behind a
+// barrier, as the shared tile does.
+template <int NDT>
+__device__ __forceinline__ void score_tile_chunked(const float* X, const float* Y, float* s_x, float* s_y, f32x16 (&s)[2][2]) {
+  if constexpr (NDT == 1) {
+    score_tile_128<1>(X, Y, s_x, s_y, s);
+  } else {
+    constexpr int64_t dp = 32 * NDT;
+    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE, i = lane & 31, h = lane >> 5;
+    const int wr = wave >> 1, wc = wave & 1;
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[m][n][r] = 0.f;
+    // Unrolled for two chunks (d <= 64), rolled above: unrolled, the chunks' operand loads are hoisted over one another and
+    // the two accumulator sets spill from d = 96 on (152 .. 752 bytes a lane at NDT 3 .. 5)
+    constexpr int CHUNKS_UNROLLED = NDT <= 2 ? NDT : 1;
+#pragma unroll CHUNKS_UNROLLED
+    for (int kc = 0; kc < NDT; ++kc) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int e = tid + BLOCK * j, rr = e >> 3, c4 = (e & 7) * 4;
+        *reinterpret_cast<float4*>(s_x + rr * LK + c4) = *reinterpret_cast<const float4*>(X + rr * dp + kc * KC + c4);
+        *reinterpret_cast<float4*>(s_y + rr * LK + c4) = *reinterpret_cast<const float4*>(Y + rr * dp + kc * KC + c4);
+      }
+      __syncthreads();
+      f32x16 c[2][2];
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) c[m][n][r] = 0.f;
+      const float* pa = s_x + (64 * wr + i) * LK + 16 * h;
+      const float* pb = s_y + (64 * wc + i) * LK + 16 * h;
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const float4 a0 = *reinterpret_cast<const float4*>(pa + 4 * q4);
+        const float4 a1 = *reinterpret_cast<const float4*>(pa + 32 * LK + 4 * q4);
+        const float4 b0 = *reinterpret_cast<const float4*>(pb + 4 * q4);
+        const float4 b1 = *reinterpret_cast<const float4*>(pb + 32 * LK + 4 * q4);
+#define IDG_SVD_SCORE_STEP(F)                                                       \
+  c[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.F, b0.F, c[0][0], 0, 0, 0);     \
+  c[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.F, b1.F, c[0][1], 0, 0, 0);     \
+  c[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.F, b0.F, c[1][0], 0, 0, 0);     \
+  c[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.F, b1.F, c[1][1], 0, 0, 0);
+        IDG_SVD_SCORE_STEP(x) IDG_SVD_SCORE_STEP(y) IDG_SVD_SCORE_STEP(z) IDG_SVD_SCORE_STEP(w)
+#undef IDG_SVD_SCORE_STEP
+      }
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[m][n][r] += c[m][n][r];
+      __syncthreads();
+    }
+  }
+}
+
 // The tile pass in its three forms.  X: the 128 rows the workgroup owns (rows of the LDS tile); Y: the tiles it walks (columns
 // of the LDS tile), tile p at Y + p * 128 * dp.
 //   MODE_SUMS / MODE_SUMS_ACC  X = a query tile, Y = the table tiles [lo, hi) of chunk blockIdx.y: the running maximum, the
@@ -283,8 +350,10 @@ __global__ __launch_bounds__(BLOCK) void svd_prep_kernel(const float* __restrict
 //                              stored maximum and coefficient of each column, acc += that . Y.
 // Wave w computes the 64 x 64 quarter (w >> 1, w & 1) of the score tile, and rows [32 w, 32 w + 32) x all columns of the second
 // product, whose A operand (the tile) comes from LDS and whose B operand (Y) straight from memory (idg_tnce.hip).
+// The score tile comes from score_tile_chunked: above d = 32 two sets of 64 score registers are live inside a chunk (the
+// chunk's own sums and the running total), one set after it.
 // Two workgroups per CU up to d = 128, except the accumulating sums form at 96 < d <= 128: its 64 accumulator registers,
-// the 64 of the score tile and the staged operands do not fit 256 registers without spilling, so it takes one.
+// the 128 of the two score sets and the staged operands do not fit 256 registers without spilling, so it takes one.
 template <int NDT, int MODE>
 __global__ __launch_bounds__(BLOCK, (NDT <= 3 || (NDT == 4 && MODE != MODE_SUMS_ACC)) ? 2 : 1) void svd_tile_kernel(
     const float* __restrict__ Xall, const float* __restrict__ Yall, int per, int n_y, int64_t n_valid, float scale2,
@@ -323,7 +392,7 @@ __global__ __launch_bounds__(BLOCK, (NDT <= 3 || (NDT == 4 && MODE != MODE_SUMS_
     const int64_t y0 = (int64_t)p * T;
     const float* Y = Yall + y0 * dp;
     f32x16 s[2][2];
-    score_tile_128<NDT>(X, Y, s_x, s_y, s);  // ---- S = X Y^T
+    score_tile_chunked<NDT>(X, Y, s_x, s_y, s);  // ---- S = X Y^T
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
       const int col = 64 * wc + 32 * n + i;

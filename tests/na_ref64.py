@@ -166,6 +166,23 @@ def grid_upstream(B):
     return -1.3 if B in (1, 129) else None
 
 
+# the cases over every built width (tests/widths.py: EVERY_NDT): (B, d) at WIDTH_T, both forms of f, the upstream of
+# grid_upstream(B)
+WIDTH_B = (129, 257)
+WIDTH_T = 0.1
+
+
+def width_seed(B, d):
+    """Apart from every seed of the grid (below 258000) and of the riders (below 8300).  Every LightCSCF case drawn from
+    these keeps KINK_GAP from the margin (tests/test_na_host.py asserts it for every case; the nearest score is 4.7e-4 off)."""
+    return 500000 + B * 1000 + d
+
+
+def width_cases(every_width):
+    """(form, B, d, T, margin, seed) of the cases over `every_width`, in all_cases()' form."""
+    return [("random", B, d, WIDTH_T, m, width_seed(B, d)) for B in WIDTH_B for d in every_width for m in GRID_M]
+
+
 def zero_rows_of(users, pos, U):
     return (int(users[2]), U + int(pos[5]))
 

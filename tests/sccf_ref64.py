@@ -117,6 +117,16 @@ def grid_upstream(B):
     return (0.7, -1.3) if B in (1, 129) else None
 
 
+# the cases over every built width (tests/widths.py: EVERY_NDT): (B, d) at WIDTH_T, the upstream pair of grid_upstream(B)
+WIDTH_B = (129, 257)
+WIDTH_T = 0.1
+
+
+def width_seed(B, d):
+    """Apart from every seed of the grid (below 258000) and of the riders (below 8300)."""
+    return 500000 + B * 1000 + d
+
+
 def zero_rows_of(users, pos, U):
     return (int(users[2]), U + int(pos[5]))
 

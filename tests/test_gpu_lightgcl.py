@@ -6,6 +6,9 @@ measured against the code under test.
   (a) idg_svd_nce_f32, both losses and all four gradient outputs, against float64 over a pruned grid in which every value of
       d in {32, 48, 64, 256}, B in {1, 127, 129, 300}, N in {1, 127, 128, 129, 1000}, q in {1, 5, 16}, both sides (row0 = 0 and
       row0 > 0), tau in {0.2, 1.0} appears; ids with repeats, and one id filling the whole batch;
+      and, on the matrix-core passes (B = 129 and 300), the widths of tests/widths.py (EVERY_NDT, LIGHTGCL_CHUNKED), which
+      launch svd_tile_kernel at every NDT = ceil(d / 32) = 1 .. 8 in its three modes (the loss-only call included; d = 128
+      with gradients is the one form of NDT <= 4 that takes a whole CU per workgroup);
   (b) the clamp: about half of the rows outside [-5, 5] on either end, none within 1e-3 of the kink; a clamped row's positive
       term has EXACTLY zero gradient;
   (c) scores near 200 (where the reference's exp overflows fp32): finite loss within tolerance, finite gradients; and scores
@@ -39,7 +42,14 @@ Batches below one tile (B <= 127) take the kernel's direct form, whose scores an
 d = 48) g_final sits 5.1e-8 of the largest entry from float64, float32 torch 5.1e-8 — what is left is the fp32 rounding of
 the view row itself.  (Through the matrix-core passes the same case sat at 2.6e-7, bound 1.2e-7: with one batch row nothing
 averages, and a weight carries the fp32 rounding of two dot products that 1 / tau multiplies.)  B = 127 and B = 128 are the
-two sides of that threshold; the engine tests run both forms (B = 96 and B = 128 batches)."""
+two sides of that threshold; the engine tests run both forms (B = 96 and B = 128 batches).
+With the cases over every built width (48 tests, 5 s without the first import; the 14 new cases under 0.2 s together):
+gradients 1.2e-7 .. 3.1e-6 of the largest entry where float32 torch sits 2.1e-7 .. 3.1e-6, at most 0.69 of the bound (g_ego at
+d = 32); losses within 1.0e-7 absolute (0.26 of the bound); the loss-only call's bits equal at every NDT.  (When these cases
+first ran, the tile passes added a score's d features in one fp32 chain: g_ego at d = 224, B = N = 129, tau = 0.2 sat 3.69e-6 of
+the largest entry from float64 — float32 torch 1.61e-6, bound 3.21e-6 — and failed, with d = 160 and d = 200 at 0.98 of their
+bounds.  The scores are now summed 32 features at a time, csrc/idg_svdnce.hip: score_tile_chunked; the same case sits at
+6.6e-7, d = 160 and d = 200 at 0.30 and 0.55 of their bounds at most.)"""
 import importlib
 import io
 import logging
@@ -53,6 +63,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from tests import lightgcl_ref64 as ref  # noqa: E402
+from tests import widths  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32, F64 = torch.float32, torch.float64
@@ -158,6 +169,30 @@ def test_kernel_vs_float64_over_the_dispatch(ops, d, B, N, q, row0, tau, ids):
         assert len(set(idv.tolist())) < B
     _check("d=%d B=%d N=%d q=%d row0=%d tau=%g %s" % (d, B, N, q, row0, tau, ids), ops, Fp, Ep, row0, N, AS, P, idv, tau,
            upstream=(0.7, -1.3))
+
+
+def _width_id(d, B, grads="gradients"):
+    one = "-one-workgroup-per-CU" if d == 128 else ""  # <4, MODE_SUMS_ACC>: the source's own launch-bounds exception
+    return "d%d-NDT%d-B%d-%s%s" % (d, widths.ndt(d), B, grads, one)
+
+
+# every NDT = ceil(d / 32) of svd_tile_kernel, all above SMALL_B (the matrix-core passes): d, B, N, q, row0, tau, ids
+WIDTH_GRID = [pytest.param(d, 129, 129, 5, 37, 0.2, "random", id=_width_id(d, 129)) for d in widths.EVERY_NDT] \
+    + [pytest.param(d, 300, 1000, 16, 0, 1.0, "same", id=_width_id(d, 300)) for d in widths.LIGHTGCL_CHUNKED]  # table chunks, query splits
+
+
+@pytest.mark.parametrize("d,B,N,q,row0,tau,ids", WIDTH_GRID)
+def test_kernel_vs_float64_over_every_built_width(ops, d, B, N, q, row0, tau, ids):
+    """<NDT, MODE_SUMS_ACC> and <NDT, MODE_TABLE> with gradients; at B = 129 the loss-only call too (<NDT, MODE_SUMS>), which
+    gives the bits of the gradient call's loss."""
+    assert B > 127
+    Fp, Ep, AS, P, idv = _case("widths", d, B, N, q, row0, ids)
+    assert len(set(idv.tolist())) < B
+    got, _ = _check("d=%d (NDT %d) B=%d N=%d q=%d row0=%d tau=%g %s" % (d, widths.ndt(d), B, N, q, row0, tau, ids), ops, Fp, Ep, row0,
+                    N, AS, P, idv, tau, upstream=(0.7, -1.3))
+    if B == 129:
+        alone = _run(ops, Fp, Ep, row0, N, AS, P, idv, float(np.float32(tau)), grads=False)
+        assert torch.equal(alone[0].view(torch.int32), got[0].view(torch.int32)), "the loss-only call gives other bits"
 
 
 # ================================================================================================================ (b) the clamp

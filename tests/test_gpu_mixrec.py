@@ -6,6 +6,8 @@ tests/mixrec_ref64.py, pinned to the reference's own numbers by tests/test_mixre
       T in {0.2, 1.0}; the identity permutation and one with fixed points; beta in {0, 1, 1e-6, 0.5}; nu one-hot and with
       zeros; duplicate ids and all-distinct ids; a zero panel row as anchor, as negative and as permutation partner;
       upstream != 1; g_panel pre-filled (the gradient is ADDED);
+      and B in {129, 257} over the widths of tests/widths.py (EVERY_NDT), which with the grid above launch every NDT =
+      ceil(d / 32) = 1 .. 8 the source instantiates, the loss-only form of each included;
   (b) the loss-only call gives the bits of the gradient call's loss; two runs give identical bits;
   (c) ops.mix_nce under autograd is the raw call;
   (d) models.MixRec against the reference's fixture (tests/golden/mixrec_small.npz), both settings, the recorded draws
@@ -27,7 +29,10 @@ points, betas (0, 1); 0.36 over the size grid; 0.6 .. 0.7 with the identity perm
 is almost all projected away), losses within 1.9e-6 relative at B = 1 and 2.9e-7 elsewhere; (d) forward() + backward() and
 the fused step 6.1e-6 (`def`) and 3.6e-6 (`mid`) of the largest entry from the fixture, the fused step 3e-8 from forward() +
 autograd; losses within 2e-7 of the fixture's; no trajectory element outside rtol 1e-4 / atol 1e-6 (largest difference
-2.6e-6)."""
+2.6e-6).
+With the cases over every built width (104 tests, 5.1 s for the whole file without the first build; the 20 new
+cases under 0.1 s together): gradients at most 0.33 of the bound (B = 129, d = 96), losses within 1.4e-7 relative, the loss-only
+call's bits equal at every NDT."""
 import os
 
 import numpy as np
@@ -37,6 +42,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from tests import mixrec_ref64 as ref  # noqa: E402
+from tests import widths  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32, F64 = torch.float32, torch.float64
@@ -157,6 +163,19 @@ def _check(tag, ops, panel, U, ids, draws, t, w=1.1, upstream=None, base=None):
 def test_kernel_vs_float64_over_sizes(ops, B, d, t):
     panel, U, ids, draws = _case("sizes", B, d)
     _check("B=%d d=%d T=%g" % (B, d, t), ops, panel, U, ids, draws, t)
+
+
+@pytest.mark.parametrize("d", widths.EVERY_NDT)
+@pytest.mark.parametrize("B", widths.B_TILES)
+def test_kernel_vs_float64_over_every_built_width(ops, B, d):
+    """Every NDT = ceil(d / 32) the source instantiates, with gradients (MODE_SUMS_ACC and the table pass) and, at B = 129,
+    through the loss-only call (MODE_SUMS) too: the bits of the gradient call's loss."""
+    panel, U, ids, draws = _case("widths", B, d)
+    _check("B=%d d=%d (NDT %d) T=0.2" % (B, d, widths.ndt(d)), ops, panel, U, ids, draws, 0.2)
+    if B == 129:
+        l1, _ = _run(ops, panel, U, ids, draws, 0.2, 1.1)
+        l0, _ = _run(ops, panel, U, ids, draws, 0.2, 1.1, grads=False)
+        assert torch.equal(l0.view(torch.int32), l1.view(torch.int32)), "the loss-only call gives other bits"
 
 
 @pytest.mark.parametrize("perm", ["identity", "fixed points"])

@@ -15,6 +15,10 @@ user, so that the gradient is the 1e5 times smaller rest of parts that cancel, a
 wrong by percents of it; next come one user repeated 96 times at T = 0.1 (1.8e-5) and the LightCCF cases of the grid at T = 0.1
 (up to 4.5e-6).  Twice 3.2e-2 is far above the cap, so the cap IS the bound: 1e-5, for every case, T = 0.05 included.  (It is
 what made the kernel a double-precision one: csrc/idg_nance.hip)
+The cases over the widths of tests/widths.py (EVERY_NDT at B = 129 and 257, T = 0.1, both forms of f; the regulariser at
+B = 129), which with the grid launch every NDT = ceil(d / 32) = 1 .. 8 the source instantiates, take the same GRAD_TOL: their
+float32 yardsticks are 9.7e-7 .. 4.3e-6 (worst: LightCCF, B = 257, d = 224; tests/test_na_host.py prints each), twice which
+is under the cap in every case — and the double-precision kernel sits far below either.
 At B = 1 the gradient is zero (LightCCF) or a rest of the same kind; the error is then divided by the scale of the parts
 (na_ref64.grad_scale has the reasoning).  A zero panel row's own gradient carries normalize()'s 1e12 and is compared on its
 own scale, at 1e-4.  Every LightCSCF case asserts, in float64, that no score lies within 1e-5 of the margin.
@@ -29,6 +33,9 @@ ops.reg_rows_raw: loss within 5.5e-8, gradient within 6.0e-8 (bound 2^-23).  The
 (`ccf_mf`), 1.6e-7 (`ccf_gcn`), 9.5e-8 (`cscf_mf`), 2.2e-7 (`cscf_gcn`); three fused steps: no element outside rtol 1e-4 /
 atol 1e-6 in any setting, 3.2e-6 off at most (`ccf_gcn`); the fused step's gradient equals forward() + autograd's bit for bit
 (the same kernels in the same order); the float-atomic path of the engine within 6.0e-8 of the deterministic one.
+With the cases over every built width (181 tests, 4.4 s; the 50 new cases under 0.1 s together): gradients at most 1.6e-7 of
+the largest entry = 0.016 of GRAD_TOL (B = 257, d = 192, LightCCF), losses within 4.9e-8 relative; ops.reg_rows_raw at B = 129
+over the same widths: loss within 3.5e-8, gradient within 5.1e-8 (bound 2^-23).
 """
 import importlib
 import io
@@ -43,6 +50,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from tests import na_ref64 as ref  # noqa: E402
+from tests import widths  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRAD_TOL = 1e-5
@@ -114,6 +122,26 @@ def test_op_matches_float64_statement(B, d, t, margin):
     _check(loss, g, panel, U, users, pos, t, margin, upstream=up, what="B=%d d=%d T=%g margin=%s" % (B, d, t, margin))
     if B >= 96:
         assert int(torch.unique(users).numel()) < B and int(torch.unique(pos).numel()) < B  # 45 / 61 rows: ids repeat
+
+
+@pytest.mark.parametrize("margin", ref.GRID_M)
+@pytest.mark.parametrize("d", widths.EVERY_NDT)
+@pytest.mark.parametrize("B", ref.WIDTH_B)
+def test_op_matches_float64_statement_over_every_built_width(B, d, margin):
+    """Every NDT = ceil(d / 32) the source instantiates, both forms of f, with gradients and, at B = 129, through the loss-only
+    call too (the same bits)."""
+    from idgrec_amd import ops
+
+    t = ref.WIDTH_T
+    panel, users, pos, U = ref.case_inputs(B, d, ref.width_seed(B, d), device="cuda")
+    up = ref.grid_upstream(B)
+    g = torch.zeros_like(panel)
+    loss = ops.na_nce_loss_raw(panel, users, pos, U, t, margin, 1.0, g, upstream=_up(up)).clone()
+    _check(loss, g, panel, U, users, pos, t, margin, upstream=up,
+           what="widths B=%d d=%d (NDT %d) T=%g margin=%s" % (B, d, widths.ndt(d), t, margin))
+    if B == 129:
+        l0 = ops.na_nce_loss_raw(panel, users, pos, U, t, margin, 1.0).clone()
+        assert torch.equal(l0, loss)  # the loss alone: the same bits as with gradients
 
 
 @pytest.mark.parametrize("margin", ref.GRID_M)
@@ -273,6 +301,11 @@ def test_reg_rows_against_float64(B, d):
     p = panel.clone().requires_grad_(True)
     (2.0 * ops.reg_rows_loss(p, users, pos, neg, U, lam)).backward()
     assert torch.equal(p.grad[rows], 2.0 * ge[rows]) and bool((p.grad[~rows] == 0).all())
+
+
+@pytest.mark.parametrize("d", widths.EVERY_NDT)
+def test_reg_rows_against_float64_over_every_built_width(d):
+    test_reg_rows_against_float64(129, d)
 
 
 # --------------------------------------------------------------------------------------- (d) the models

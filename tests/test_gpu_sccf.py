@@ -10,6 +10,9 @@ float64 gradient = twice the worst float32 yardstick tests/test_sccf_host.py mea
 it (tests/sccf_ref64.py: RIDERS) and the fixture — 2.11e-6, one user repeated 129 times at T = 1 — rounded up to two digits;
 tighter than the siblings' 1e-5, which would otherwise cap it.  A zero panel row's own gradient
 carries normalize()'s 1e12 and is compared on its own scale, at the siblings' 1e-4.
+The cases over the widths of tests/widths.py (EVERY_NDT at B = 129 and 257, T = 0.1), which with grid (a) launch every NDT =
+ceil(d / 32) = 1 .. 8 the source instantiates, take GRAD_TOL unchanged: their worst float32 yardstick is 7.7e-7 (B = 257,
+d = 32; tests/test_sccf_host.py).
 
 Measured on an MI355X (70 tests, 32 s).  The kernel's gradients over grid (a): at most 8.0e-7 of the largest entry = 0.19 of
 GRAD_TOL (B = 257, d = 48, T = 0.1), 1.2e-7 ... 3.2e-7 at T = 1; the riders: all-distinct ids at most 2.9e-7, zero rows 4.4e-7, one
@@ -19,6 +22,8 @@ failed; the factor is now kept in double and every chain has 32 terms.)  Losses 
 elsewhere.  The plugin's .grad against the fixture: 8.3e-7 (`mf`), 5.8e-7 (`gcn`); three fused steps: no element outside rtol
 1e-4 / atol 1e-6, 3.0e-8 (`mf`) and 5.2e-6 (`gcn`) off at most; the fused step's gradient equals forward() + autograd's bit for
 bit (the same kernels in the same order).
+With the cases over every built width (90 tests, 4.2 s; the 20 new cases under 0.1 s together): gradients at most 1.08e-6 of
+the largest entry = 0.25 of GRAD_TOL (B = 129, d = 32), 3.0e-7 at B = 257, d = 200; losses within 6.6e-8 relative.
 """
 import importlib
 import io
@@ -33,6 +38,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from tests import sccf_ref64 as ref  # noqa: E402
+from tests import widths  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRAD_TOL = 4.3e-6
@@ -106,6 +112,24 @@ def test_op_matches_float64_statement(B, d, t):
     _check(loss, g, panel, U, users, pos, t, upstream=pair, what="B=%d d=%d T=%g" % (B, d, t))
     if B >= 96:
         assert int(torch.unique(users).numel()) < B and int(torch.unique(pos).numel()) < B  # 45 / 61 rows: ids repeat
+
+
+@pytest.mark.parametrize("d", widths.EVERY_NDT)
+@pytest.mark.parametrize("B", ref.WIDTH_B)
+def test_op_matches_float64_statement_over_every_built_width(B, d):
+    """Every NDT = ceil(d / 32) the source instantiates, with gradients and, at B = 129, through the loss-only call too (the
+    same bits).  GRAD_TOL unchanged: tests/test_sccf_host.py measures the float32 yardstick of these cases below half of it."""
+    from idgrec_amd import ops
+
+    t = ref.WIDTH_T
+    panel, users, pos, U = ref.case_inputs(B, d, ref.width_seed(B, d), device="cuda")
+    pair = ref.grid_upstream(B)
+    g = torch.zeros_like(panel)
+    loss = ops.sccf_loss_raw(panel, users, pos, U, t, g, upstream=_up(pair)).clone()
+    _check(loss, g, panel, U, users, pos, t, upstream=pair, what="widths B=%d d=%d (NDT %d) T=%g" % (B, d, widths.ndt(d), t))
+    if B == 129:
+        l0 = ops.sccf_loss_raw(panel, users, pos, U, t).clone()
+        assert torch.equal(l0, loss)  # the loss alone: the same bits as with gradients
 
 
 def _riders(*forms):

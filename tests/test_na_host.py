@@ -30,6 +30,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from tests import na_ref64 as ref  # noqa: E402
+from tests import widths  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "na_small.npz")
@@ -203,6 +204,33 @@ def test_float32_yardstick_is_measured(golden_small):
     print("float32 yardstick: losses %.2e (%s); gradients %.2e of the largest entry (%s)" % (worst_l + worst_g))
     assert worst_l[0] < 1e-5
     assert 2 * worst_g[0] >= GRAD_CAP  # the bound of tests/test_gpu_na.py is min(2 * yardstick, cap) = the cap
+
+
+def test_every_built_width_case_is_away_from_the_margin_and_its_yardstick_is_measured():
+    """The cases tests/test_gpu_na.py runs over tests/widths.py's EVERY_NDT (the same seeds, on the CPU): every LightCSCF case
+    keeps KINK_GAP from the margin, and the float32 yardstick of each is printed.  Twice the worst of them (4.3e-6: LightCCF,
+    B = 257, d = 224) stays under GRAD_CAP, so these cases take tests/test_gpu_na.py's GRAD_TOL = GRAD_CAP unchanged."""
+    worst_l, worst_g, gap_min = (0.0, None), (0.0, None), 1.0
+    seeds = set()
+    for form, B, d, t, m, seed in ref.width_cases(widths.EVERY_NDT):
+        seeds.add(seed)
+        panel, users, pos, U = ref.case_inputs(B, d, seed, form=form)
+        if m is not None:
+            gap = ref.kink_distance(panel, U, users, pos, m)
+            gap_min = min(gap_min, gap)
+            assert gap > ref.KINK_GAP, (B, d, gap)
+        up = ref.grid_upstream(B)
+        l64, g64 = ref.panel_terms(panel, U, users, pos, t, m, upstream=up)
+        l32, g32 = ref.panel_terms(panel, U, users, pos, t, m, dtype=torch.float32, upstream=up)
+        e_l = float(((l32.double() - l64) / l64).abs())
+        e_g = float((g32.double() - g64).abs().max()) / ref.grad_scale(panel, U, users, pos, t, m, g64, upstream=up)
+        name = "widths B=%d d=%d T=%g margin=%s" % (B, d, t, m)
+        print("%s: losses %.2e, gradients %.2e of the largest entry" % (name, e_l, e_g))
+        worst_l, worst_g = max(worst_l, (e_l, name)), max(worst_g, (e_g, name))
+    print("every built width: losses %.2e (%s); gradients %.2e of the largest entry (%s); smallest distance from the margin %.2e"
+          % (worst_l + worst_g + (gap_min,)))
+    assert worst_l[0] < 1e-5 and 2 * worst_g[0] <= GRAD_CAP
+    assert not seeds & {s for c in ref.all_cases() for s in c[5:]}  # no seed of the older cases is drawn again
 
 
 @pytest.mark.parametrize("tag", TAGS)

@@ -15,7 +15,8 @@ losses 1.42e-7, gradients 8.5e-7 (T = 0.1) and 4.1e-7 (T = 1); the cases riding 
 2.4e-7, zero rows 3.7e-7, store / accumulate 3.4e-7, and one user repeated B times 9.6e-7 (B = 96), 8.5e-7 (B = 257) and 2.11e-6
 (B = 129, d = 48, T = 1: there the two terms' shares of the one user row's gradient nearly cancel, and the rounding of Z and of
 the row sums is amplified about tenfold).  The worst gradient figure is 2.11e-6: twice that, rounded up to two digits, is
-tests/test_gpu_sccf.py's GRAD_TOL = 4.3e-6 (tighter than the siblings' 1e-5, which caps it).  The
+tests/test_gpu_sccf.py's GRAD_TOL = 4.3e-6 (tighter than the siblings' 1e-5, which caps it).  The cases over every built
+width (tests/widths.py: EVERY_NDT at B = 129 and 257, T = 0.1): losses 1.2e-7, gradients 2.5e-7 .. 7.7e-7 (B = 257, d = 32). The
 reference's own float32 run on the fixture's three batches: `mf` no element outside rtol 1e-4 / atol 1e-6 (8.9e-8 off at
 most), `gcn` 2.8e-5 of the elements outside, 1.2e-5 off at most."""
 import importlib
@@ -30,6 +31,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from tests import sccf_ref64 as ref  # noqa: E402
+from tests import widths  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "sccf_small.npz")
@@ -171,6 +173,20 @@ def test_float32_yardstick_is_measured(golden_small):
         worst_l, worst_g[t] = max(worst_l, e_l), max(worst_g[t], e_g)
     print("grid (a) with its riders: losses %.2e; gradients %.2e (T = 0.1), %.2e (T = 1)" % (worst_l, worst_g[0.1], worst_g[1.0]))
     assert worst_l < 1e-5 and max(worst_g.values()) <= WORST_YARDSTICK
+
+
+def test_float32_yardstick_over_every_built_width():
+    """The same measurement on the cases tests/test_gpu_sccf.py runs over tests/widths.py's EVERY_NDT (the same seeds, on the
+    CPU): none above the figure GRAD_TOL was taken from, so those cases take GRAD_TOL unchanged."""
+    worst_l, worst_g = (0.0, None), (0.0, None)
+    for B in ref.WIDTH_B:
+        for d in widths.EVERY_NDT:
+            panel, users, pos, Uc = ref.case_inputs(B, d, ref.width_seed(B, d))
+            e_l, e_g = _yardstick(panel, Uc, users, pos, ref.WIDTH_T, upstream=ref.grid_upstream(B))
+            print("widths B=%d d=%d T=%g: float32 literal form: losses %.2e, gradients %.2e of the largest entry" % (B, d, ref.WIDTH_T, e_l, e_g))
+            worst_l, worst_g = max(worst_l, (e_l, (B, d))), max(worst_g, (e_g, (B, d)))
+    print("every built width: losses %.2e (B, d = %s); gradients %.2e (B, d = %s)" % (worst_l + worst_g))
+    assert worst_l[0] < 1e-5 and worst_g[0] <= WORST_YARDSTICK
 
 
 @pytest.mark.parametrize("tag", TAGS)
