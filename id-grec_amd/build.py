@@ -17,7 +17,7 @@ OBJ = os.path.join(HERE, "build")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libidgrec.so")
 SOURCES = ["idg_host.cpp", "idg_comm.cpp", "idg_stream.cpp", "idg_step.cpp", "idg_graph.hip", "idg_bpr.hip", "idg_score.hip", "idg_ssl.hip", "idg_dense.hip",
-           "idg_ngcf.hip", "idg_gccf.hip", "idg_gcmc.hip", "idg_group.hip", "idg_intent.hip", "idg_shard.hip", "idg_au.hip", "idg_sccf.hip", "idg_nance.hip", "idg_vae.hip", "idg_tnce.hip", "idg_mixnce.hip", "idg_svdnce.hip", "idg_kmeans.hip", "idg_rownorm.hip"]
+           "idg_ngcf.hip", "idg_gccf.hip", "idg_gcmc.hip", "idg_group.hip", "idg_intent.hip", "idg_hyper.hip", "idg_shard.hip", "idg_au.hip", "idg_sccf.hip", "idg_nance.hip", "idg_vae.hip", "idg_tnce.hip", "idg_mixnce.hip", "idg_svdnce.hip", "idg_kmeans.hip", "idg_rownorm.hip"]
 ARCH = "gfx950"
 
 

@@ -189,6 +189,16 @@ PROTOTYPES = {
     "idg_intent_bwd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "idg_intent_bwd_f32": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int64,
                                      C.c_int64, c_vp, C.c_uint64, C.c_uint64, c_vp, C.c_int64, c_vp, c_vp, c_vp]),
+    "idg_hyper_latent_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "idg_hyper_latent_f32": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int64, C.c_int64, c_vp, C.c_int64, C.c_int64, C.c_int64, C.c_float, c_vp,
+                                       C.c_uint64, C.c_uint64, c_vp, c_vp, c_vp, c_vp]),
+    "idg_hyper_expand_f32": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int64, C.c_int64, c_vp, C.c_int64, C.c_int64, C.c_float, c_vp, C.c_uint64,
+                                       C.c_uint64, c_vp, C.c_int64, c_vp, C.c_int64, c_vp, C.c_int64, c_vp, C.c_int64, c_vp]),
+    "idg_hyper_bwd_f32": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int64, C.c_int64, c_vp, C.c_int64, c_vp, C.c_int64, c_vp, c_vp, C.c_int64,
+                                    C.c_int64, C.c_float, c_vp, C.c_uint64, C.c_uint64, c_vp, C.c_int64, c_vp, C.c_int64, C.c_int, c_vp]),
+    "idg_hyper_close_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "idg_hyper_close_f32": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int64, C.c_int64, c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int64,
+                                      c_vp, c_vp, c_vp]),
     "idg_colsum_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "idg_colsum_f32": (C.c_int, [c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp, C.c_int, c_vp, c_vp]),
     "idg_copy_cols_f32": (C.c_int, [c_vp, C.c_int64, c_vp, C.c_int64, C.c_int64, C.c_int64, c_vp]),

@@ -1810,6 +1810,145 @@ def intent_mix(X, W, row0=0, stream=None, noise=None):
     return X + T * noise, T
 
 
+# ----------------------------------------------------------------------------------- HCCF's hypergraph layer
+_hyper_ws = {}
+
+
+def _hyper_workspace(device, d=64, h=64):
+    ws = _hyper_ws.get((d, h, device))
+    if ws is None:
+        nbytes = max(int(lib.idg_hyper_latent_workspace_bytes(d, h)), int(lib.idg_hyper_close_workspace_bytes(d, h)), 16)
+        ws = _hyper_ws[(d, h, device)] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _mask_base(mask, base_row):
+    """Pointer of GLOBAL row 0 of a contiguous uint8 / bool [., h] mask panel whose first row is global row base_row."""
+    if mask is None:
+        return None
+    if mask.dtype not in (torch.uint8, torch.bool) or not mask.is_contiguous():
+        raise TypeError("hyper mask must be a contiguous uint8 or bool panel (got %s, contiguous=%s)" % (mask.dtype, mask.is_contiguous()))
+    return mask.data_ptr() - int(base_row) * int(mask.shape[1])
+
+
+def _hyper_rows(P, row0, base_row, nrows):
+    return P.shape[0] - (int(row0) - int(base_row)) if nrows is None else int(nrows)
+
+
+def hyper_latent_raw(E0, W, X, L, row0=0, nrows=None, keep=1.0, mask=None, seed=0, stream_id=0, mask_out=None, base_row=0, ws=None):
+    """idg_hyper_latent_f32 on global rows row0 .. row0 + nrows - 1: L [h, d] = H^T . X with H = M o (E0 . W) / keep.  The
+    panels' (and masks') first row is global row base_row (default 0: whole panels; row0 >= base_row); leading dimensions are
+    the tensors' row strides.  mask: uint8 / bool [., h], else the generator's of (seed, stream_id)."""
+    _require_device(E0, W, X, L, mask, mask_out)
+    d, h = W.shape
+    ws = _hyper_workspace(E0.device, d, h) if ws is None else ws
+    check(lib.idg_hyper_latent_f32(_row_base(E0, base_row), _ld(E0), _ptr(W), d, h, _row_base(X, base_row), _ld(X), int(row0),
+                                   _hyper_rows(X, row0, base_row, nrows), float(keep), _mask_base(mask, base_row), C.c_uint64(seed),
+                                   C.c_uint64(stream_id), _ptr(L), _mask_base(mask_out, base_row), _ptr(ws), _stream()),
+          "idg_hyper_latent_f32")
+    return L
+
+
+def hyper_expand_raw(E0, W, L, Y, row0=0, nrows=None, keep=1.0, mask=None, seed=0, stream_id=0, side=None, next=None, total=None,
+                     base_row=0):
+    """idg_hyper_expand_f32: Y = H . L; with side and next: next = side + Y; with total: total += next (+= Y without side)."""
+    _require_device(E0, W, L, Y, mask, side, next, total)
+    d, h = W.shape
+    ld = lambda t: 0 if t is None else _ld(t)  # noqa: E731
+    check(lib.idg_hyper_expand_f32(_row_base(E0, base_row), _ld(E0), _ptr(W), d, h, _ptr(L), int(row0), _hyper_rows(Y, row0, base_row, nrows),
+                                   float(keep), _mask_base(mask, base_row), C.c_uint64(seed), C.c_uint64(stream_id),
+                                   _row_base(Y, base_row), _ld(Y), _row_base(side, base_row), ld(side), _row_base(next, base_row), ld(next),
+                                   _row_base(total, base_row), ld(total), _stream()), "idg_hyper_expand_f32")
+    return Y
+
+
+def hyper_bwd_raw(E0, W, X, gY, L, gL, gX, gHb, row0=0, nrows=None, keep=1.0, mask=None, seed=0, stream_id=0, accumulate=False,
+                  base_row=0):
+    """idg_hyper_bwd_f32: gX += H . gL;  gHb = (accumulate ? gHb : 0) + M o (gY . L^T + X . gL^T) / keep."""
+    _require_device(E0, W, X, gY, L, gL, gX, gHb, mask)
+    d, h = W.shape
+    check(lib.idg_hyper_bwd_f32(_row_base(E0, base_row), _ld(E0), _ptr(W), d, h, _row_base(X, base_row), _ld(X), _row_base(gY, base_row),
+                                _ld(gY), _ptr(L), _ptr(gL), int(row0), _hyper_rows(X, row0, base_row, nrows), float(keep),
+                                _mask_base(mask, base_row), C.c_uint64(seed), C.c_uint64(stream_id), _row_base(gX, base_row), _ld(gX),
+                                _row_base(gHb, base_row), _ld(gHb), int(bool(accumulate)), _stream()), "idg_hyper_bwd_f32")
+    return gX, gHb
+
+
+def hyper_close_raw(E0, W, gHb, gE0, gW, row0=0, nrows=None, base_row=0, ws=None):
+    """idg_hyper_close_f32: gE0 += gHb . W^T;  gW [d, h] = E0^T . gHb (stored)."""
+    _require_device(E0, W, gHb, gE0, gW)
+    d, h = W.shape
+    ws = _hyper_workspace(E0.device, d, h) if ws is None else ws
+    check(lib.idg_hyper_close_f32(_row_base(E0, base_row), _ld(E0), _ptr(W), d, h, _row_base(gHb, base_row), _ld(gHb), int(row0),
+                                  _hyper_rows(E0, row0, base_row, nrows), _row_base(gE0, base_row), _ld(gE0), _ptr(gW), _ptr(ws), _stream()),
+          "idg_hyper_close_f32")
+    return gE0, gW
+
+
+class _HyperMix(torch.autograd.Function):
+    """Y = H . (H^T . X) at (d, h) = (64, 64) on csrc/idg_hyper.hip's four kernels.  Saved: E0, W, X, L (64 x 64) and the mask
+    panel when one was passed in; H is recomputed and the mask regenerated from (seed, stream id, global row)."""
+
+    @staticmethod
+    def forward(ctx, E0, W, X, row0, keep, stream, mask):
+        seed, sid = stream
+        L, Y = torch.empty_like(W), torch.empty_like(X)
+        kw = dict(row0=row0, keep=keep, mask=mask, seed=seed, stream_id=sid, base_row=row0)
+        hyper_latent_raw(E0, W, X, L, **kw)
+        hyper_expand_raw(E0, W, L, Y, **kw)
+        ctx.save_for_backward(E0, W, X, L, mask)
+        ctx.kw = kw
+        return Y
+
+    @staticmethod
+    def backward(ctx, gY):
+        E0, W, X, L, mask = ctx.saved_tensors
+        kw = ctx.kw
+        gY = _f32c(gY, "gY")
+        gL, gW = torch.empty_like(L), torch.empty_like(W)
+        gX, gE0 = torch.zeros_like(X), torch.zeros_like(E0)
+        gHb = torch.empty((E0.shape[0], W.shape[1]), dtype=torch.float32, device=E0.device)
+        hyper_latent_raw(E0, W, gY, gL, **kw)
+        hyper_bwd_raw(E0, W, X, gY, L, gL, gX, gHb, accumulate=False, **kw)
+        hyper_close_raw(E0, W, gHb, gE0, gW, row0=kw["row0"], base_row=kw["base_row"])
+        return gE0, gW, gX, None, None, None, None
+
+
+def hyper_mix(E0, W, X, row0=0, keep=1.0, stream=None, mask=None):
+    """One side of HCCF's hypergraph layer (models/HCCF.py:56-74): with Hb = E0 @ W [n, h] and H = M * Hb / keep it returns
+    Y = H @ (H.T @ X) [n, d], differentiable in E0, W and X.  M ~ Bernoulli(keep): `mask` (uint8 / bool [n, h]) when given, else
+    the counter-based keep function of (seed, stream id, row0 + r, c) — row0 is the global row of the panels' first row, so
+    the two sides of one panel draw different masks from one stream; keep >= 1 keeps everything.  (d, h) = (64, 64): the four
+    kernels of csrc/idg_hyper.hip, H never stored; any other width composes torch operators under autograd, and draws a
+    missing mask with torch.rand (NOT the kernels' function of the stream).  stream: (seed, stream id); default: the next one
+    of the device seed's sequence."""
+    for t, name in ((E0, "E0"), (W, "W"), (X, "X")):
+        if t.dtype != torch.float32:
+            raise TypeError("hyper_mix: %s must be float32 (got %s)" % (name, t.dtype))
+    if E0.dim() != 2 or W.dim() != 2 or X.dim() != 2 or E0.shape[1] != W.shape[0] or X.shape[0] != E0.shape[0]:
+        raise ValueError("hyper_mix: E0 [n, d], W [d, h] and X [n, d'] do not fit (got %s, %s, %s)"
+                         % (tuple(E0.shape), tuple(W.shape), tuple(X.shape)))
+    if E0.shape[0] == 0:
+        raise ValueError("hyper_mix: E0 has 0 rows")
+    if mask is not None and tuple(mask.shape) != (E0.shape[0], W.shape[1]):
+        raise ValueError("hyper_mix: mask %s must be [n, h] = %s" % (tuple(mask.shape), (E0.shape[0], W.shape[1])))
+    if int(row0) < 0 or not float(keep) > 0.0:
+        raise ValueError("hyper_mix: row0 = %d must not be negative and keep = %g must be positive" % (int(row0), float(keep)))
+    if not (E0.is_cuda and W.is_cuda and X.is_cuda and (mask is None or mask.is_cuda)):
+        raise RuntimeError("hyper_mix: runs on MI355X only (got E0 on %s, W on %s, X on %s); there is no CPU fallback"
+                           % (E0.device, W.device, X.device))
+    keep = float(keep)
+    if tuple(W.shape) == (64, 64) and X.shape[1] == 64:
+        stream = _next_noise_stream() if stream is None else stream
+        mask = None if mask is None else mask.contiguous()
+        return _HyperMix.apply(_f32c(E0, "E0"), _f32c(W, "W"), _f32c(X, "X"), int(row0), keep, stream, mask)
+    Hb = E0 @ W
+    if mask is None and keep < 1.0:
+        mask = torch.rand(Hb.shape, device=Hb.device) < keep
+    H = Hb if mask is None else Hb * (mask.to(Hb.dtype) / min(keep, 1.0))
+    return H @ (H.t() @ X)
+
+
 # ----------------------------------------------------------------------------------- InfoNCE
 
 

@@ -706,6 +706,37 @@ size_t idg_intent_bwd_workspace_bytes(int64_t d, int64_t k);
 int idg_intent_bwd_f32(const float* gF, int64_t ldgf, const float* gT_in, int64_t ldgt, const uint32_t* gt_rows,
                        const uint32_t* rows_bitmap, const float* X, int64_t ldx, int64_t row0, int64_t nrows, const float* W, int64_t d, int64_t k, const float* noise,
                        uint64_t seed, uint64_t stream_id, float* gX, int64_t ldgx, float* gW, void* ws, void* stream);
+/* HCCF's hypergraph layer on rows row0 .. row0 + nrows - 1 of ONE side of the panel (models/HCCF.py:56-74; csrc/idg_hyper.hip),
+ * (d, h) = (64, 64), fp32:  Hb = E0 . W [., h],  H = M o Hb / keep,  L = H^T . X [h, d],  Y = H . L.  H is never stored: every
+ * call recomputes it from E0 and W (one product order everywhere: the backward's H has the forward's bits) and regenerates
+ * the mask.  Every panel and the mask are indexed by the GLOBAL row (the pointers are those of row 0); row0 need not be a
+ * multiple of the 64-row tile.  M[row, c] = `mask`[row * h + c] != 0 (a uint8 panel [., h]) when given, else
+ * idg_dropout's published keep function of (seed, stream_id, row, c) at p = 1 - keep; keep >= 1 keeps every element of the
+ * generator's.  W, L, gL and gW are contiguous [64, 64].
+ *   idg_hyper_latent_f32: L (stored) = sum over the rows of H[r, :]^T . X[r, :]; with gY as X it gives gL.  mask_out
+ *     (nullable, uint8 [., h]) receives the mask that was used.
+ *   idg_hyper_expand_f32: Y = H . L; with side (and next, which come together): next = side + Y; with total (nullable):
+ *     total += next (+= Y without side).
+ *   idg_hyper_bwd_f32: gX += H . gL;  gHb = (accumulate ? gHb : 0) + M o (gY . L^T + X . gL^T) / keep  ([., h] panel).
+ *   idg_hyper_close_f32: gE0 += gHb . W^T;  gW [d, h] = E0^T . gHb (stored).
+ * L, gL and gW are summed in a fixed order (row slices on persistent workgroups, added in slice order): two runs give the
+ * same bits.  Any other (d, h), NULL or misaligned pointers (panels, matrices and ws 16 bytes, masks 4), nrows <= 0,
+ * row0 < 0, keep <= 0, a leading dimension below 64 or not a multiple of 4, side without next, and outputs that overlap
+ * inputs or each other: IDG_E_INVALID before any device work.  ws: as many bytes as the call's *_workspace_bytes returns (0
+ * for widths that are not built; both are 512 slices of [64, 64] floats, one per resident workgroup). */
+size_t idg_hyper_latent_workspace_bytes(int64_t d, int64_t h);
+int idg_hyper_latent_f32(const float* E0, int64_t lde, const float* W, int64_t d, int64_t h, const float* X, int64_t ldx, int64_t row0,
+                         int64_t nrows, float keep, const uint8_t* mask, uint64_t seed, uint64_t stream_id, float* L, uint8_t* mask_out,
+                         void* ws, void* stream);
+int idg_hyper_expand_f32(const float* E0, int64_t lde, const float* W, int64_t d, int64_t h, const float* L, int64_t row0, int64_t nrows,
+                         float keep, const uint8_t* mask, uint64_t seed, uint64_t stream_id, float* Y, int64_t ldy, const float* side,
+                         int64_t lds, float* next, int64_t ldn, float* total, int64_t ldtot, void* stream);
+int idg_hyper_bwd_f32(const float* E0, int64_t lde, const float* W, int64_t d, int64_t h, const float* X, int64_t ldx, const float* gY,
+                      int64_t ldgy, const float* L, const float* gL, int64_t row0, int64_t nrows, float keep, const uint8_t* mask,
+                      uint64_t seed, uint64_t stream_id, float* gX, int64_t ldgx, float* gHb, int64_t ldgh, int accumulate, void* stream);
+size_t idg_hyper_close_workspace_bytes(int64_t d, int64_t h);
+int idg_hyper_close_f32(const float* E0, int64_t lde, const float* W, int64_t d, int64_t h, const float* gHb, int64_t ldgh, int64_t row0,
+                        int64_t nrows, float* gE0, int64_t ldge, float* gW, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * DEVICE: in-batch InfoNCE between two views, forward + backward
