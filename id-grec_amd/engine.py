@@ -10,9 +10,10 @@ operators in ops.py execute (tests compare the two), so models may use either.
 Embedding layout: ONE [num_users + num_items, d] panel, users first; the model's two
 nn.Embedding weights are views into it (no torch.cat per step).
 
-For the models whose step is a chain of its own (ngcf.py, gccf.py, bigcf.py, egcf.py) the end of the file holds what they
-share: BatchPrep (the batch's index-only work, one batch ahead), plan_infonce (the InfoNCE id lists as part of it) and
-PanelEngine (the constructor state, the flat buffer of small tensors and the common call sites).
+BatchPrep (the batch's index-only work, one batch ahead) is the slot ring of every engine: PropagationEngine is one, the
+models whose step is a chain of its own (ngcf.py, gccf.py, bigcf.py, egcf.py) hold one.  For those the end of the file has
+what else they share: plan_infonce (the InfoNCE id lists as part of that work) and PanelEngine (the constructor state, the
+flat buffer of small tensors and the common call sites).
 """
 import ctypes as C
 import os
@@ -92,7 +93,136 @@ class StepPlan:
             pass
 
 
-class PropagationEngine:
+class BatchPrep:
+    """The index-only work of a batch — the bitmap of its <= 3B panel rows, (optionally) the live work units of that bitmap
+    on a graph, the sorted scatter plan of its (row, slot) pairs — on a SIDE stream, one batch ahead of the step that uses
+    it.  PropagationEngine is one (its own work in _index_work, its own two-stage wait); the engines with their own step hold
+    one (EgcfEngine / EgcfAltEngine, and the PanelEngine subclasses NgcfEngine, GccfEngine, BigcfEngine).
+    Three slots: the batch being processed, the one prepared ahead, and one whose last step the host has seen complete.
+
+        prep.prefetch(users, pos, neg)            # the trainer's lookahead (optional)
+        slot = prep.take(users, pos, neg)         # the step: finds the prepared slot (or prepares now), orders the main
+        ...  slot.bitmap / slot.units / slot.ws   #   stream behind it
+        prep.release(slot)                        # after the last launch that reads them
+    """
+
+    class _Slot:
+        def __init__(self, words, device):
+            self.bitmap = torch.zeros(words, dtype=torch.int32, device=device)
+            self.units, self.units_B = None, -1  # live work units of the bitmap (Graph.live_units), rebuilt with it
+            self.ws, self.ws_B = None, -1
+            self.plan_done, self.free_ev = ops.LocalEvent(), ops.LocalEvent()
+            self.free = None  # = free_ev once recorded on the main stream: the step that used this slot is done
+            self.key, self.ids = None, None
+            self.stamp = 0    # order of last hand-out (the ring recycles the oldest)
+
+    def __init__(self, num_users, n_rows, dim, device, units_graph=None, extra=None):
+        """extra(slot, users, pos, neg, raw_stream): more index-only work of the batch, enqueued on the side stream before the
+        slot's `plan_done` event (EgcfEngine, BigcfEngine: plan_infonce, the id lists of their InfoNCE calls)."""
+        self.U, self.n, self.d, self.device, self.graph = int(num_users), int(n_rows), int(dim), device, units_graph
+        self.extra = extra
+        self._slots = [self._Slot((self.n + 31) // 32, device) for _ in range(3)]  # (three: see the pacing in _pace)
+        self._ends = []  # end-of-step events of the last two steps, older first
+        self._paced = os.environ.get("IDG_PACE", "1") != "0"
+        # side stream for index-only work, claimed at construction (ops.side_stream: hardware-queue placement)
+        self._side = ops.side_stream(device)
+        self._side_raw = self._side.cuda_stream  # launches name their stream explicitly
+        self._fork = ops.LocalEvent()  # device-local events (ops.LocalEvent) throughout
+        self._id_storage = None  # storages of the id tensors last ordered against the main stream
+        self._stamp = 0
+
+    def _fresh(self, slot, B):
+        """Will preparing a batch of B triples in `slot` (re)allocate one of its workspaces?"""
+        return slot.ws_B != B
+
+    def _prepare(self, slot, users, pos, neg):
+        main = torch.cuda.current_stream()
+        B = int(users.shape[0])
+        # Workspaces come from torch's caching allocator on the MAIN stream but are first written by the SIDE stream: a block
+        # recycled from a tensor whose last reader is still queued on main must not be overwritten early (ADVICE r04) — any
+        # (re)allocation (a new batch size: the short last batch of an epoch) orders the side stream behind main once
+        fresh = self._fresh(slot, B)
+        if slot.ws_B != B:
+            slot.ws, slot.ws_B = ops.bpr_workspace(B, self.d, self.device), B
+        if slot.free is not None:
+            slot.free.wait(self._side_raw)     # the step that last used this slot has consumed it
+        # The side stream must not read the ids before the main stream has produced them.  Batches are slices of
+        # one epoch-long tensor: ordering after the main stream once per storage is enough (doing it per batch would
+        # also queue this batch's index work behind the previous step's kernels: measured +6 us/step).
+        src = (users.untyped_storage().data_ptr(), pos.untyped_storage().data_ptr(), neg.untyped_storage().data_ptr())
+        if slot.free is None or src != self._id_storage or fresh:
+            self._id_storage = src
+            self._fork.record(main.cuda_stream)
+            self._fork.wait(self._side_raw)
+        self._index_work(slot, users, pos, neg, B)
+        slot.plan_done.record(self._side_raw)  # needed by the gradient scatter (and by the InfoNCE calls behind it)
+        slot.key = (users.data_ptr(), pos.data_ptr(), neg.data_ptr(), B)
+        slot.ids = (users, pos, neg)  # keeps the id tensors alive until the side stream has read them (a caller's temporaries
+        #                               would otherwise return to the allocator, and be rewritten, while still being read)
+
+    def _touch_rows(self, slot, users, pos, neg, B):
+        ops.bpr_touch_rows_raw(users, pos, neg, self.U, slot.bitmap, stream=self._side_raw, clear_bits=self.n)
+        if self.graph is not None:
+            # the bitmap's rows as a list of work units: a row-restricted product then runs one wave per unit instead of
+            # visiting every tile (same bits)
+            slot.units = self.graph.live_units(slot.bitmap, 3 * B, ws=slot.units if slot.units_B == B else None,
+                                               stream=self._side_raw)
+            slot.units_B = B
+
+    def _index_work(self, slot, users, pos, neg, B):
+        """The batch's index-only launches, all on the side stream, between the fork ordering and `plan_done`."""
+        self._touch_rows(slot, users, pos, neg, B)
+        ops.bpr_plan_raw(users, pos, neg, self.U, self.n, self.d, ws=slot.ws, stream=self._side_raw)
+        if self.extra is not None:
+            self.extra(slot, users, pos, neg, self._side_raw)
+
+    def _take_slot(self):
+        """Next slot of the ring: one whose batch has been consumed the longest ago (or never filled); when every slot
+        holds an unconsumed prefetch, the oldest of those is recycled."""
+        free = [sl for sl in self._slots if sl.key is None]
+        slot = min(free if free else self._slots, key=lambda sl: sl.stamp)
+        self._stamp += 1
+        slot.stamp = self._stamp
+        return slot
+
+    def prefetch(self, users, pos, neg):
+        self._prepare(self._take_slot(), users, pos, neg)
+
+    def _lookup(self, users, pos, neg):
+        """(slot, ahead): the slot prepared for this batch (ahead = True: by prefetch(), during the previous step), or one
+        taken and prepared right now."""
+        key = (users.data_ptr(), pos.data_ptr(), neg.data_ptr(), int(users.shape[0]))
+        slot = next((sl for sl in self._slots if sl.key == key), None)
+        ahead = slot is not None
+        if slot is None:
+            slot = self._take_slot()
+            self._prepare(slot, users, pos, neg)
+        slot.key = None
+        return slot, ahead
+
+    def _pace(self):
+        """The host enqueues a step in less time than the device runs it and would get hundreds of steps ahead; it blocks
+        until the step before the previous one has finished (two steps stay queued: the device never runs dry)."""
+        if self._paced and len(self._ends) >= 2:
+            self._ends[-2].synchronize()
+
+    def take(self, users, pos, neg):
+        slot, ahead = self._lookup(users, pos, neg)
+        # a batch prepared ahead is, with the pacing, known to be ready when its step is enqueued, and the step's stream
+        # needs no wait (PropagationEngine._take_rows: 4.5 us per barrier packet)
+        self._pace()
+        if not (ahead and self._paced and slot.plan_done.query()):
+            slot.plan_done.wait(torch.cuda.current_stream().cuda_stream)
+        return slot
+
+    def release(self, slot):
+        slot.free = slot.free_ev
+        slot.free.record(torch.cuda.current_stream().cuda_stream)
+        del self._ends[:-1]  # (also when not paced: the list must not grow by an entry per step)
+        self._ends.append(slot.free)
+
+
+class PropagationEngine(BatchPrep):
     def __init__(self, graph, num_users, num_items, dim, n_layers, include_layer0=True, reg_lambda=1e-4, lr=1e-3,
                  betas=(0.9, 0.999), eps=1e-8, deterministic=True, params=None):
         self.graph = graph  # None => no propagation (MFBPR)
@@ -114,23 +244,19 @@ class PropagationEngine:
         self.exp_avg = self.exp_avg_sq = None                 # Adam moments: allocated by the first train_step()
         self.final = torch.empty((self.n, self.d), **f32) if graph is not None else None
         self.g_final = torch.zeros((self.n, self.d), **f32) if graph is not None else None
-        words = (self.n + 31) // 32
+        # the slot ring and its side stream (BatchPrep): the deterministic forms only — float atomics need no scatter plan
         # two slots: the batch being processed and the one prepared ahead (measured: 3 or 4 change nothing)
         # three prepared-batch slots: the batch in its step, the one prepared ahead, and one whose last user (two steps back)
         # the host has SEEN complete — see _pace()
-        self._slots = [self._Slot(words if graph is not None else 1, dev) for _ in range(3)] if self.deterministic else None
-        self._ends = []  # end-of-step events of the last steps, oldest first
-        self._paced = os.environ.get("IDG_PACE", "1") != "0"
+        if self.deterministic:
+            BatchPrep.__init__(self, self.U, self.n, self.d, dev, units_graph=graph)
+        else:
+            self._slots = self._side = self._side_raw = None
         self._touched = None
-        self._stamp = 0
         self._loss3 = torch.zeros(3, **f32)  # [bpr, reg_lambda * reg, ssl_lambda * InfoNCE]
         self.loss = self._loss3[:2]
         self.step_count = 0
         self._final_version = -1  # step_count the cached propagation belongs to
-        # side stream for index-only work, claimed at construction (ops.side_stream: hardware-queue placement)
-        self._side = ops.side_stream(dev) if self.deterministic else None
-        self._side_raw = self._side.cuda_stream if self._side is not None else None  # launches name their stream explicitly
-        self._fork = ops.LocalEvent() if self._side is not None else None  # device-local events (ops.LocalEvent) throughout
         # Receptive-field propagation (plain LightGCN step, K = 2 or 3): layer K is read at the batch's rows, so layer
         # k is produced on their (K - k)-hop neighbourhood only, and the gradient flows back through the same sets —
         # exact, and most of every product on a graph much larger than that neighbourhood (configs[4]: 15 M rows, the
@@ -145,8 +271,7 @@ class PropagationEngine:
         # GPU: 0.2732 vs 0.2692 ms/step on one box.
         self._compact = (self.graph is not None and self.deterministic and os.environ.get("IDG_COMPACT_INPUTS", "0") == "1"
                          and self.graph.nnz * 8 <= (2 << 30))
-        self._id_storage = None  # storages of the id tensors last ordered against the main stream
-        self._pp = None     # ping-pong panels of the instrumented (layer-by-layer) forward
+        self._pp = None    # ping-pong panels of the instrumented (layer-by-layer) forward
         self.fuse_adam = True  # train_step(): Adam in the last backward epilogue (False: separate idg_adam_step_f32)
         self.ssl = None        # (eps, temperature, ssl_lambda): SimGCL's perturbed views + InfoNCE inside the fused step
         self.xssl = None       # the same triple for XSimGCL (one perturbed pass, cl_layer = 1)
@@ -201,54 +326,31 @@ class PropagationEngine:
         return self.final
 
     # ---- index-only preparation of a batch on the side stream (row bitmap + sorted scatter plan)
-    class _Slot:
+    class _Slot(BatchPrep._Slot):
         def __init__(self, words, device):
-            self.bitmap = torch.zeros(words, dtype=torch.int32, device=device)
-            self.units, self.units_B = None, -1  # live work units of the bitmap (Graph.live_units), rebuilt with it
+            super().__init__(words, device)
             self.compact = None  # the tiles' entry lists compacted to the bitmap's rows (Graph.compact_inputs), rebuilt with it
             self.hops = None  # [rows of the batch, + 1 hop, + 2 hops ...] (receptive-field propagation)
             self.use_fields = False
-            self.ids = None
-            self.ws = None
             self.ssl_ws, self.ssl_key, self.ssl_B = None, None, -1  # InfoNCE workspace holding this batch's id lists (ops.infonce_plan_raw)
-            self.key = None
-            self.rows_done = self.plan_done = None
-            self.free = None  # = free_ev once recorded on the main stream: the step that used this slot is done
-            self.free_ev = None
-            self.stamp = 0    # order of last hand-out (the ring recycles the oldest)
+            self.rows_done = ops.LocalEvent()  # bitmap, unit list and hop sets are complete: what the forward needs
 
     def _prepare(self, slot, users, pos, neg):
         if self.au is not None or self.sccf is not None:
             neg = pos  # bitmap and scatter plan of users and positives only (idg_align_uniform_f32's plan form)
-        main = torch.cuda.current_stream()
-        B = users.shape[0]
+        BatchPrep._prepare(self, slot, users, pos, neg)
+
+    def _ssl_form(self):
+        return self.graph is not None and (self.ssl is not None or self.xssl is not None or self.sgl is not None)
+
+    def _fresh(self, slot, B):
+        return (BatchPrep._fresh(self, slot, B) or (self.graph is not None and slot.units_B != B)
+                or (self._ssl_form() and (slot.ssl_ws is None or slot.ssl_B != B)))
+
+    def _index_work(self, slot, users, pos, neg, B):
         slot.ssl_key = None  # a plan is honoured for the batch it was built for only: set again below
-        # Workspaces come from torch's caching allocator on the MAIN stream but are first written by the SIDE stream: a block
-        # recycled from a tensor whose last reader is still queued on main must not be overwritten early — any
-        # (re)allocation (a new batch size: the short last batch of an epoch) orders the side stream behind main once
-        ssl_form = self.graph is not None and (self.ssl is not None or self.xssl is not None or self.sgl is not None)
-        fresh = (slot.ws is None or slot.ws_B != B or (self.graph is not None and slot.units_B != B)
-                 or (ssl_form and (slot.ssl_ws is None or slot.ssl_B != B)))
-        if slot.ws is None or slot.ws_B != B:
-            slot.ws, slot.ws_B = ops.bpr_workspace(B, self.d, self.device), B
-            slot.rows_done, slot.plan_done, slot.free_ev = ops.LocalEvent(), ops.LocalEvent(), ops.LocalEvent()
-        if slot.free is not None:
-            slot.free.wait(self._side_raw)     # the step that last used this slot has consumed it
-        # The side stream must not read the ids before the main stream has produced them.  Batches are slices of
-        # one epoch-long tensor: ordering after the main stream once per storage is enough (doing it per batch would
-        # also queue this batch's index work behind the previous step's kernels: measured +6 us/step).
-        src = (users.untyped_storage().data_ptr(), pos.untyped_storage().data_ptr(), neg.untyped_storage().data_ptr())
-        if slot.free is None or src != self._id_storage or fresh:
-            self._id_storage = src
-            self._fork.record(main.cuda_stream)
-            self._fork.wait(self._side_raw)
         if self.graph is not None:  # (without propagation nothing is restricted to the batch's rows: MFBPR)
-            ops.bpr_touch_rows_raw(users, pos, neg, self.U, slot.bitmap, stream=self._side_raw, clear_bits=self.n)
-            # the bitmap's rows as a list of work units: the row-restricted last layer then runs one wave per unit
-            # instead of visiting every tile (same bits)
-            slot.units = self.graph.live_units(slot.bitmap, 3 * B, ws=slot.units if slot.units_B == B else None,
-                                               stream=self._side_raw)
-            slot.units_B = B
+            self._touch_rows(slot, users, pos, neg, B)
             # (... and much larger than THIS batch's neighbourhood: with ~256 distinct two-hop rows per batch row the
             #  field of a 2^20-triple batch is the graph, and the restricted kernels only cost: 355 vs 342 ms measured)
             slot.use_fields = self._fields and 3 * B * 256 <= self.n
@@ -263,7 +365,7 @@ class PropagationEngine:
                     self.graph.expand_rows(slot.hops[j - 1], slot.hops[j], stream=self._side_raw)
             slot.rows_done.record(self._side_raw)  # needed by the last forward layer
         ops.bpr_plan_raw(users, pos, neg, self.U, self.n, self.d, ws=slot.ws, stream=self._side_raw)
-        if self.graph is not None and (self.ssl is not None or self.xssl is not None or self.sgl is not None):
+        if self._ssl_form():
             # the id-list stage of the step's InfoNCE call (unique rows of the batch; SGL: raw lists, their repeat flags
             # and positions) is index-only too: ~19 us of small launches per call off the main stream
             mode = ops.SSL_RAW if self.sgl is not None else ops.SSL_UNIQUE
@@ -271,28 +373,6 @@ class PropagationEngine:
                 slot.ssl_ws, slot.ssl_B = ops.infonce_workspace(self.n, B, self.d, self.device), B
             ops.infonce_plan_raw(users, pos, self.U, self.n, self.d, mode, slot.ssl_ws, stream=self._side_raw)
             slot.ssl_key = (B, mode)
-        slot.plan_done.record(self._side_raw)  # needed by the gradient scatter (and by the InfoNCE call behind it)
-        slot.key = (users.data_ptr(), pos.data_ptr(), neg.data_ptr(), B)
-        slot.ids = (users, pos, neg)  # keeps the id tensors alive until the side stream has read them (a caller's temporaries
-        #                               would otherwise return to the allocator, and be rewritten, while still being read)
-
-    @staticmethod
-    def _ssl_plan(slot, users, mode):
-        """Keyword arguments of the step's InfoNCE call: the slot's workspace with the id lists already in it — when this
-        slot was prepared for this batch size and list form (an engine switched to an SSL form after a prefetch: no)."""
-        if slot.ssl_ws is not None and slot.ssl_key == (int(users.shape[0]), mode):
-            return {"ws": slot.ssl_ws, "planned": True}
-        return {}
-
-    def _take_slot(self):
-        """Next slot of the ring: one whose batch has been consumed the longest ago (or never filled); when every slot
-        holds an unconsumed prefetch, the oldest of those is recycled."""
-        free = [sl for sl in self._slots if sl.key is None]
-        pool = free if free else self._slots
-        slot = min(pool, key=lambda sl: sl.stamp)
-        self._stamp += 1
-        slot.stamp = self._stamp
-        return slot
 
     def prefetch(self, users, pos, neg):
         """Optional one-batch lookahead: prepare the NEXT batch's row bitmap and scatter plan now, so
@@ -302,7 +382,7 @@ class PropagationEngine:
             if self._plan_eligible(int(users.shape[0])):
                 self._next = (users, pos, neg)  # prepared by the NEXT train_step() call, inside the library
             else:
-                self._prepare(self._take_slot(), users, pos, neg)
+                BatchPrep.prefetch(self, users, pos, neg)
 
     def _plan_eligible(self, B):
         """The one-call step covers the plain form: deterministic scatter, Adam in the epilogue, no SSL views, no gradient
@@ -371,6 +451,35 @@ class PropagationEngine:
         ops.na_nce_loss_raw(final, users, pos, self.U, temperature, margin, weight, g_final, loss=loss[k:k + 1],
                             accumulate=True, plan_ws=plan_ws)
 
+    def _batch_loss(self, final, g_final, g_ego, users, pos, neg, loss, plan_ws=None, store=False, touched=None):
+        """The step's first loss call on the batch's rows of `final`, whichever the modes name, then _na_call.  plan_ws: the
+        slot's scatter plan (None: float atomics).  store=False: gradient rows are ADDED into the zeroed panels g_final
+        (d loss / d final) and g_ego (the regulariser's share; the same panel without a graph).  store=True (the row-restricted
+        step): reached rows of both are STORED — exactly the rows of `touched`, the slot's bitmap — and the backward
+        propagation reads flagged rows only: neither panel is ever zero-filled."""
+        if self.au is not None:
+            # DirectAU: the alignment / uniformity call in place of the BPR scatter
+            ops.align_uniform_raw(final, self.params, users, pos, self.U, self.au[0], self.reg_lambda, g_final, g_ego,
+                                  loss=loss[:3] if store else loss, accumulate=not store, plan_ws=plan_ws)
+        elif self.sccf is not None:
+            # SCCF: the same place and contract; no term on the ego rows, so its rows of g_ego are stored as zeros
+            ops.sccf_loss_raw(final, users, pos, self.U, self.sccf[0], g_final, g_ego if store else None,
+                              loss=loss[:2] if store else loss, accumulate=not store, plan_ws=plan_ws)
+        elif self.na is not None and not self.na[3]:
+            # LightCSCF: no BPR term — the regulariser's rows of g_ego are STORED, and (store=True) zeros to the same rows of
+            # g_final (users, positives and negatives: the bitmap's rows), before the call below ADDS its rows
+            ops.reg_rows_raw(self.params, users, pos, neg, self.U, self.reg_lambda, g_ego=g_ego,
+                             g_final=g_final if store else None, loss=loss[0:1], plan_ws=plan_ws)
+        else:
+            # (store=True: the bitmap already holds the batch's rows: with TOUCHED_PRESET the scatter stores its rows without
+            #  writing it, so the lists registered for it — the compacted inputs of the first backward product — stay valid)
+            det = 0 if plan_ws is None else (2 | native.IDG_BPR_TOUCHED_PRESET) if store else 2
+            ops.bpr_fused_raw(final, self.params, users, pos, neg, self.U, self.reg_lambda, g_final, g_ego, loss=loss[:2],
+                              deterministic=det, touched=touched, ws=plan_ws)
+        # LightCCF / LightCSCF: d(weight * na) / d final joins in g_final's rows — users and positives are a subset of the
+        # bitmap — where SimGCL's InfoNCE gradient joins (_loss_rows)
+        self._na_call(final, users, pos, g_final, loss, plan_ws)
+
     # ---- forward + backward: losses [bpr, reg_lambda*reg] and d(sum)/dE0 into self.grad
     @torch.no_grad()
     def loss_and_grad(self, users, pos, neg, loss_out=None, _adam_step=0):
@@ -382,7 +491,6 @@ class PropagationEngine:
         three = (self.ssl is not None or self.xssl is not None or self.sgl is not None or self.au is not None
                  or (self.na is not None and self.na[3]))
         loss = (self._loss3 if three else self.loss) if loss_out is None else loss_out
-        main = torch.cuda.current_stream()
         if self.au is not None and self.sccf is not None:
             raise ValueError("PropagationEngine: au and sccf both replace the BPR call; set one of them")
         if self.na is not None and (self.au is not None or self.sccf is not None):
@@ -391,104 +499,90 @@ class PropagationEngine:
         if self.au is not None or self.sccf is not None:
             neg = pos  # (the slot key and plan of a DirectAU / SCCF batch: see _prepare)
         if self.graph is None:
-            self.grad.zero_()
-            if self.sccf is not None and not self.deterministic:
-                ops.sccf_loss_raw(self.params, users, pos, self.U, self.sccf[0], self.grad, loss=loss)
-                return loss
-            if self.au is not None and not self.deterministic:
-                ops.align_uniform_raw(self.params, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.grad,
-                                      self.grad, loss=loss)
-                return loss
-            if not self.deterministic:
-                if self.na is not None and not self.na[3]:
-                    ops.reg_rows_raw(self.params, users, pos, neg, self.U, self.reg_lambda, g_ego=self.grad, loss=loss[0:1])
-                else:
-                    ops.bpr_fused_raw(self.params, self.params, users, pos, neg, self.U, self.reg_lambda, self.grad,
-                                      self.grad, loss=loss[:2], deterministic=0)
-                self._na_call(self.params, users, pos, self.grad, loss, None)
-                return loss
-            # the sorted scatter plan depends on the indices only: prepared on the side stream (by prefetch() during the
-            # previous step, or right now) — in-call it is half of an MFBPR step
-            key = (users.data_ptr(), pos.data_ptr(), neg.data_ptr(), users.shape[0])
-            slot = next((sl for sl in self._slots if sl.key == key), None)
-            if slot is None:
-                slot = self._take_slot()
-                self._prepare(slot, users, pos, neg)
-            slot.key = None
-            slot.plan_done.wait(main.cuda_stream)
-            if self.au is not None:
-                ops.align_uniform_raw(self.params, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.grad,
-                                      self.grad, loss=loss, plan_ws=slot.ws)
-            elif self.sccf is not None:
-                ops.sccf_loss_raw(self.params, users, pos, self.U, self.sccf[0], self.grad, loss=loss, plan_ws=slot.ws)
-            elif self.na is not None and not self.na[3]:
-                ops.reg_rows_raw(self.params, users, pos, neg, self.U, self.reg_lambda, g_ego=self.grad, loss=loss[0:1],
-                                 plan_ws=slot.ws)
-            else:
-                ops.bpr_fused_raw(self.params, self.params, users, pos, neg, self.U, self.reg_lambda, self.grad,
-                                  self.grad, loss=loss[:2], deterministic=2, ws=slot.ws)
-            self._na_call(self.params, users, pos, self.grad, loss, slot.ws)
-            slot.free = slot.free_ev
-            slot.free.record(main.cuda_stream)
-            self._final_version = -1
-            return loss
+            return (self._step_mf_planned if self.deterministic else self._step_mf_atomic)(users, pos, neg, loss)
         if not self.deterministic:
-            self.grad.zero_()
-            self.g_final.zero_()
-            self.graph.propagate_mean_raw(self.params, self.K, self.inc, out=self.final)
-            if self.au is not None:
-                ops.align_uniform_raw(self.final, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.g_final,
-                                      self.grad, loss=loss)
-            elif self.sccf is not None:
-                ops.sccf_loss_raw(self.final, users, pos, self.U, self.sccf[0], self.g_final, loss=loss)
-            elif self.na is not None and not self.na[3]:
-                ops.reg_rows_raw(self.params, users, pos, neg, self.U, self.reg_lambda, g_ego=self.grad, loss=loss[0:1])
-            else:
-                ops.bpr_fused_raw(self.final, self.params, users, pos, neg, self.U, self.reg_lambda, self.g_final,
-                                  self.grad, loss=loss[:2], deterministic=0)
-            self._na_call(self.final, users, pos, self.g_final, loss, None)
-            self.graph.propagate_mean_bwd_raw(self.g_final, self.K, self.inc, out=self.grad, accumulate=True)
-            self._final_version = -1
-            return loss
-        # deterministic path.  The batch's rows are flagged in a bitmap and its (row, slot) pairs sorted —
-        # index-only work done on a side stream (by prefetch() during the previous step, or right now).
-        key = (users.data_ptr(), pos.data_ptr(), neg.data_ptr(), users.shape[0])
-        slot = next((sl for sl in self._slots if sl.key == key), None)
-        ahead = slot is not None
-        if slot is None:  # not prefetched: prepare it now (the main stream then waits for the side stream)
-            slot = self._take_slot()
-            self._prepare(slot, users, pos, neg)
-        slot.key = None
+            return self._step_atomic(users, pos, neg, loss)
+        return self._step_rows(users, pos, neg, loss, three, _adam_step)
+
+    def _step_mf_atomic(self, users, pos, neg, loss):
+        """No graph, float atomics: the loss gradient is the gradient."""
+        self.grad.zero_()
+        self._batch_loss(self.params, self.grad, self.grad, users, pos, neg, loss)
+        return loss
+
+    def _step_mf_planned(self, users, pos, neg, loss):
+        """No graph, deterministic.  The sorted scatter plan depends on the indices only: prepared on the side stream (by
+        prefetch() during the previous step, or right now) — in-call it is half of an MFBPR step."""
+        self.grad.zero_()
+        slot, _ = self._lookup(users, pos, neg)
+        slot.plan_done.wait(torch.cuda.current_stream().cuda_stream)
+        self._batch_loss(self.params, self.grad, self.grad, users, pos, neg, loss, plan_ws=slot.ws)
+        self._finish(slot)
+        return loss
+
+    def _step_atomic(self, users, pos, neg, loss):
+        """Graph, float atomics: full propagations around a scatter into zeroed panels."""
+        self.grad.zero_()
+        self.g_final.zero_()
+        self.graph.propagate_mean_raw(self.params, self.K, self.inc, out=self.final)
+        self._batch_loss(self.final, self.g_final, self.grad, users, pos, neg, loss)
+        self.graph.propagate_mean_bwd_raw(self.g_final, self.K, self.inc, out=self.grad, accumulate=True)
+        self._final_version = -1
+        return loss
+
+    def _step_rows(self, users, pos, neg, loss, three, adam_step):
+        """Graph, deterministic: every product restricted to the batch's rows.  They are flagged in a bitmap and the batch's
+        (row, slot) pairs sorted — index-only work done on a side stream (by prefetch() during the previous step, or right
+        now)."""
+        main = torch.cuda.current_stream()
+        slot, ahead = self._lookup(users, pos, neg)  # not prefetched: the main stream then waits for the side stream
         self.touched = slot.bitmap
-        # Pacing.  The host enqueues a step in less time than the device runs it and would get hundreds of steps ahead; it
-        # now blocks until the step before the previous one has finished (two steps stay queued: the device never runs dry).
-        # A batch prepared ahead — its preparation started when ITS slot's last step, three back, had finished — is then
-        # complete by the time its step is enqueued, the host can see that (event query), and the step's stream does not
-        # need the wait: a barrier packet costs 4.5 us between two kernels whether or not its event has fired.
-        if self._paced and len(self._ends) >= 2:
-            self._ends[-2].synchronize()
-        del self._ends[:-2]  # (also when not paced: the list must not grow by an entry per step)
+        # Pacing (_pace).  A batch prepared ahead — its preparation started when ITS slot's last step, three back, had
+        # finished — is then complete by the time its step is enqueued, the host can see that (event query), and the step's
+        # stream does not need the wait: a barrier packet costs 4.5 us between two kernels whether or not its event has fired.
+        self._pace()
         ready = ahead and self._paced and slot.plan_done.query()
         if not ready:
             (slot.plan_done if ahead else slot.rows_done).wait(main.cuda_stream)
+        self._forward_rows(slot, users)
+        assert self.exchange is None or not three, "gradient-row exchange: LightGCN-family steps only"
+        if not ahead:
+            slot.plan_done.wait(main.cuda_stream)
+        self._loss_rows(slot, users, pos, neg, loss)
+        if self.sgl is not None:
+            self._backward_sgl(slot, adam_step)
+        elif self.xssl is not None:
+            self._backward_xssl(slot, adam_step)
+        else:
+            self._backward_plain(slot, loss, three, adam_step)
+        self._finish(slot)
+        return loss
+
+    def _finish(self, slot):
+        """A step's epilogue: the slot is consumed (release: its end-of-step event), the cached propagation is stale."""
+        self.release(slot)
+        self._final_version = -1
+
+    def _alloc_views(self, count):
+        """The SSL forms' extra panels (views, then scratch or gradient panels) and InfoNCE loss pair, on first use."""
+        if self._views is None:
+            self._views = tuple(torch.empty_like(self.params) for _ in range(count))
+            self._ssl_loss = torch.zeros(2, dtype=torch.float32, device=self.device)
+
+    def _forward_rows(self, slot, users):
         if self.ssl is not None:
             # SimGCL (models/SimGCL.py:62-66): the clean pass and two perturbed ones, read at rows of the batch only
             # (unique users / positives are a subset of the bitmap); the first product is shared between the passes
-            eps, temperature, ssl_lambda = self.ssl
-            if self._views is None:
-                self._views = tuple(torch.empty_like(self.params) for _ in range(4))  # two views + two scratch panels
-                self._ssl_loss = torch.zeros(2, dtype=torch.float32, device=self.device)
+            self._alloc_views(4)  # two views + two scratch panels
             streams = [ops._next_noise_stream(), ops._next_noise_stream()]  # the sequence ops.propagate_views draws
-            ops.propagate_views_raw(self.graph, self.params, self.K, self.inc, eps, streams,
+            ops.propagate_views_raw(self.graph, self.params, self.K, self.inc, self.ssl[0], streams,
                                     [self.final, self._views[0], self._views[1]], out_rows=slot.bitmap,
                                     scratch=self._views[2:])
         elif self.xssl is not None:
             # XSimGCL (models/XSimGCL.py:40-60): ONE perturbed pass; BPR reads its layer mean, InfoNCE contrasts the
             # first layer's output with that mean.  Both are wanted at rows of the batch only.
-            eps, temperature, ssl_lambda = self.xssl
-            if self._views is None:
-                self._views = (torch.empty_like(self.params), torch.empty_like(self.params))  # (layer-1 view, its gradient)
-                self._ssl_loss = torch.zeros(2, dtype=torch.float32, device=self.device)
+            eps = self.xssl[0]
+            self._alloc_views(2)  # (layer-1 view, its gradient)
             stream = ops._next_noise_stream()
             self.graph.propagate_mean_noise_raw(self.params, self.K, self.inc, eps, stream[0], stream[1], out=self.final,
                                                 out_rows=slot.bitmap)
@@ -504,132 +598,104 @@ class PropagationEngine:
         if self.sgl is not None:
             # SGL (models/SGL.py:75-101): the same encoder on two edge-dropped sub-graphs of this epoch; their layer
             # means are contrasted at the batch's users / positives (raw ids, duplicates count)
-            temperature, ssl_lambda, sub_1, sub_2 = self.sgl
-            if self._views is None:
-                self._views = tuple(torch.empty_like(self.params) for _ in range(4))  # two views, their gradients
-                self._ssl_loss = torch.zeros(2, dtype=torch.float32, device=self.device)
+            sub_1, sub_2 = self.sgl[2:]
+            self._alloc_views(4)  # two views, their gradients
             for sub in (sub_1, sub_2):  # copies of the full graph's handle share its schedule: the same unit list serves
                 if getattr(sub, "_base", None) is self.graph and slot.units is not None:
                     sub.bind_live_units(slot.bitmap, slot.units, 3 * users.shape[0])
             sub_1.propagate_mean_raw(self.params, self.K, self.inc, out=self._views[0], out_rows=slot.bitmap)
             sub_2.propagate_mean_raw(self.params, self.K, self.inc, out=self._views[1], out_rows=slot.bitmap)
-        assert self.exchange is None or not three, "gradient-row exchange: LightGCN-family steps only"
-        if not ahead:
-            slot.plan_done.wait(main.cuda_stream)
-        if self.au is not None:
-            # DirectAU: the alignment / uniformity call in place of the BPR scatter; its rows of g_final and self.grad are
-            # stored (accumulate=False) — exactly the bitmap's rows, the contract the backward propagation below reads
-            ops.align_uniform_raw(self.final, self.params, users, pos, self.U, self.au[0], self.reg_lambda, self.g_final,
-                                  self.grad, loss=loss[:3], accumulate=False, plan_ws=slot.ws)
-        elif self.sccf is not None:
-            # SCCF: the same place and contract; no term on the ego rows, so its rows of self.grad are stored as zeros
-            ops.sccf_loss_raw(self.final, users, pos, self.U, self.sccf[0], self.g_final, self.grad, loss=loss[:2],
-                              accumulate=False, plan_ws=slot.ws)
-        # reached rows of g_final and of the regulariser gradient (self.grad) are STORED and the backward
-        # propagation reads flagged rows only: neither panel is ever zero-filled
-        # (the bitmap already holds the batch's rows: with TOUCHED_PRESET the scatter stores its rows without writing it, so
-        #  the lists registered for it — the compacted inputs of the first backward product — stay valid)
-        elif self.na is not None and not self.na[3]:
-            # LightCSCF on LightGCN: no BPR term — the regulariser's rows of self.grad are STORED, and zeros to the same rows
-            # of g_final (users, positives and negatives: the bitmap's rows), before the call below ADDS its rows
-            ops.reg_rows_raw(self.params, users, pos, neg, self.U, self.reg_lambda, g_ego=self.grad, g_final=self.g_final,
-                             loss=loss[0:1], plan_ws=slot.ws)
-        else:
-            ops.bpr_fused_raw(self.final, self.params, users, pos, neg, self.U, self.reg_lambda, self.g_final,
-                              self.grad, loss=loss[:2], deterministic=2 | native.IDG_BPR_TOUCHED_PRESET, touched=slot.bitmap,
-                              ws=slot.ws)
-        # LightCCF / LightCSCF: d(weight * na) / d final joins in g_final's (stored) rows — users and positives are a subset
-        # of the bitmap — where SimGCL's InfoNCE gradient joins below
-        self._na_call(self.final, users, pos, self.g_final, loss, slot.ws)
+
+    def _infonce(self, slot, view_1, view_2, users, pos, g_1, g_2, temperature, ssl_lambda, loss, dedup=True):
+        """ssl_lambda * InfoNCE(view_1, view_2) over the batch's users / positives (dedup: unique ids; False: raw, duplicates
+        count) into loss[2], its gradients ADDED, times ssl_lambda, into g_1 / g_2.  The id lists come from the slot's
+        workspace when it was prepared for this batch size and list form (an engine switched to an SSL form after a
+        prefetch: no)."""
+        mode = ops.SSL_UNIQUE if dedup else ops.SSL_RAW
+        planned = slot.ssl_ws is not None and slot.ssl_key == (int(users.shape[0]), mode)
+        ops.infonce_pair_raw(view_1, view_2, users, pos, self.U, temperature, g1=g_1, g2=g_2, loss=self._ssl_loss, dedup=dedup,
+                             grad_scale=ssl_lambda, accumulate=True, **({"ws": slot.ssl_ws, "planned": True} if planned else {}))
+        torch.sum(self._ssl_loss, dim=0, keepdim=True, out=loss[2:3])
+        loss[2:3].mul_(ssl_lambda)
+
+    def _loss_rows(self, slot, users, pos, neg, loss):
+        """The step's loss calls on the batch's rows of the forward's panels; every gradient row is STORED or joins a stored
+        row, in g_final (d loss / d final) and self.grad (the regulariser's share)."""
+        self._batch_loss(self.final, self.g_final, self.grad, users, pos, neg, loss, plan_ws=slot.ws, store=True,
+                         touched=slot.bitmap)
         if self.ssl is not None:
             # d(ssl_lambda * InfoNCE)/d view_1 + d(...)/d view_2 join the BPR gradient in g_final's (stored) rows
-            ops.infonce_pair_raw(self._views[0], self._views[1], users, pos, self.U, temperature, g1=self.g_final,
-                                 g2=self.g_final, loss=self._ssl_loss, grad_scale=ssl_lambda, accumulate=True,
-                                 **self._ssl_plan(slot, users, ops.SSL_UNIQUE))
-            torch.sum(self._ssl_loss, dim=0, keepdim=True, out=loss[2:3])
-            loss[2:3].mul_(ssl_lambda)
+            self._infonce(slot, self._views[0], self._views[1], users, pos, self.g_final, self.g_final, self.ssl[1], self.ssl[2],
+                          loss)
         if self.sgl is not None:
             g_1, g_2 = self._views[2], self._views[3]
             g_1.zero_()
             g_2.zero_()
-            ops.infonce_pair_raw(self._views[0], self._views[1], users, pos, self.U, temperature, g1=g_1, g2=g_2,
-                                 loss=self._ssl_loss, dedup=False, grad_scale=ssl_lambda, accumulate=True,
-                                 **self._ssl_plan(slot, users, ops.SSL_RAW))
-            torch.sum(self._ssl_loss, dim=0, keepdim=True, out=loss[2:3])
-            loss[2:3].mul_(ssl_lambda)
-            # three encoders, three backward propagations (each sub-graph is its own symmetric operator), one gradient
-            self.graph.propagate_mean_bwd_raw(self.g_final, self.K, self.inc, out=self.grad, accumulate=True, mask=slot.bitmap)
-            sub_1.propagate_mean_bwd_raw(g_1, self.K, self.inc, out=self.grad, accumulate=True)
-            sub_2.propagate_mean_bwd_raw(g_2, self.K, self.inc, out=self.grad, accumulate=True)
-            if _adam_step > 0:
-                ops.adam_step_raw(self.params, self.grad, self.exp_avg, self.exp_avg_sq, self.lr, _adam_step, self.betas[0],
-                                  self.betas[1], self.eps)
-            slot.free = slot.free_ev
-            slot.free.record(main.cuda_stream)
-            self._ends.append(slot.free)
-            self._final_version = -1
-            return loss
-        if self.xssl is not None:
+            self._infonce(slot, self._views[0], self._views[1], users, pos, g_1, g_2, self.sgl[0], self.sgl[1], loss,
+                          dedup=False)
+        elif self.xssl is not None:
             # InfoNCE(layer-1 view, layer mean): the mean's share joins the BPR gradient in g_final's stored rows; the
-            # view's share (added into its own, cleared, panel) reaches E0 through one more product, A . g_view, below
+            # view's share (added into its own, cleared, panel) reaches E0 through one more product, A . g_view
+            # (_backward_xssl)
             g_view = self._views[1]
             g_view.zero_()
-            ops.infonce_pair_raw(self._views[0], self.final, users, pos, self.U, temperature, g1=g_view, g2=self.g_final,
-                                 loss=self._ssl_loss, grad_scale=ssl_lambda, accumulate=True,
-                                 **self._ssl_plan(slot, users, ops.SSL_UNIQUE))
-            torch.sum(self._ssl_loss, dim=0, keepdim=True, out=loss[2:3])
-            loss[2:3].mul_(ssl_lambda)
-            if _adam_step > 0 and self.K >= 2 and not self.inc:
-                # d loss / d E0 = (A g + .. + A^K g) / K + A g_view = A ((g + A (g + ..)) / K + g_view): the Horner chain with
-                # its division moved in front of the LAST product, whose input then also carries the view's gradient rows
-                # (added by the step before it: sum_out accumulates into the panel the InfoNCE call filled) and whose
-                # epilogue applies Adam — no extra product for A . g_view, no separate Adam pass, no gradient panel
-                # (round 4: -28 us of a 430 us step; rounding differs from the form below in the last place)
-                bm, K = slot.bitmap, self.K
-                if getattr(self, "_xb", None) is None:
-                    self._xb = [torch.empty_like(self.params), torch.empty_like(self.params)]
-                X, xr = self.g_final, bm
-                for k in range(1, K - 1):  # h <- A . h + g
-                    ops.spmm_epi_raw(self.graph, X, Y=self._xb[(k - 1) & 1], addend=self.g_final, mask=bm, x_rows=xr)
-                    X, xr = self._xb[(k - 1) & 1], None
-                ops.spmm_epi_raw(self.graph, X, sum_in=self.g_final, sum_out=g_view, div=float(K), accumulate=True, mask=bm,
-                                 x_rows=xr)
-                ops.spmm_epi_raw(self.graph, g_view, sum_out=self.grad, accumulate=True, mask=bm,
-                                 adam=(self.params, self.exp_avg, self.exp_avg_sq, self.lr, _adam_step, self.betas[0],
-                                       self.betas[1], self.eps), adam_discard_grad=not self.store_grad)
-            else:
-                self.graph.propagate_mean_bwd_raw(self.g_final, self.K, self.inc, out=self.grad, accumulate=True, mask=slot.bitmap)
-                # grad += A . g_view (d view / d E0 = A for the first layer): live rows of g_view are the batch's unique
-                # users and positives, a subset of the bitmap (its other rows read zeros)
-                ops.spmm_ex_raw(self.graph, g_view, sum_in=self.grad, sum_out=self.grad, x_rows=slot.bitmap)
-                if _adam_step > 0:
-                    ops.adam_step_raw(self.params, self.grad, self.exp_avg, self.exp_avg_sq, self.lr, _adam_step, self.betas[0],
-                                      self.betas[1], self.eps)
-            slot.free = slot.free_ev
-            slot.free.record(main.cuda_stream)
-            self._ends.append(slot.free)
-            self._final_version = -1
-            return loss
+            self._infonce(slot, self._views[0], self.final, users, pos, g_view, self.g_final, self.xssl[1], self.xssl[2], loss)
+
+    def _backward_sgl(self, slot, adam_step):
+        # three encoders, three backward propagations (each sub-graph is its own symmetric operator), one gradient
+        sub_1, sub_2 = self.sgl[2:]
+        self.graph.propagate_mean_bwd_raw(self.g_final, self.K, self.inc, out=self.grad, accumulate=True, mask=slot.bitmap)
+        sub_1.propagate_mean_bwd_raw(self._views[2], self.K, self.inc, out=self.grad, accumulate=True)
+        sub_2.propagate_mean_bwd_raw(self._views[3], self.K, self.inc, out=self.grad, accumulate=True)
+        if adam_step > 0:
+            ops.adam_step_raw(self.params, self.grad, self.exp_avg, self.exp_avg_sq, self.lr, adam_step, self.betas[0],
+                              self.betas[1], self.eps)
+
+    def _backward_xssl(self, slot, adam_step):
+        g_view = self._views[1]
+        if adam_step > 0 and self.K >= 2 and not self.inc:
+            # d loss / d E0 = (A g + .. + A^K g) / K + A g_view = A ((g + A (g + ..)) / K + g_view): the Horner chain with
+            # its division moved in front of the LAST product, whose input then also carries the view's gradient rows
+            # (added by the step before it: sum_out accumulates into the panel the InfoNCE call filled) and whose
+            # epilogue applies Adam — no extra product for A . g_view, no separate Adam pass, no gradient panel
+            # (round 4: -28 us of a 430 us step; rounding differs from the form below in the last place)
+            bm, K = slot.bitmap, self.K
+            if getattr(self, "_xb", None) is None:
+                self._xb = [torch.empty_like(self.params), torch.empty_like(self.params)]
+            X, xr = self.g_final, bm
+            for k in range(1, K - 1):  # h <- A . h + g
+                ops.spmm_epi_raw(self.graph, X, Y=self._xb[(k - 1) & 1], addend=self.g_final, mask=bm, x_rows=xr)
+                X, xr = self._xb[(k - 1) & 1], None
+            ops.spmm_epi_raw(self.graph, X, sum_in=self.g_final, sum_out=g_view, div=float(K), accumulate=True, mask=bm,
+                             x_rows=xr)
+            ops.spmm_epi_raw(self.graph, g_view, sum_out=self.grad, accumulate=True, mask=bm,
+                             adam=(self.params, self.exp_avg, self.exp_avg_sq, self.lr, adam_step, self.betas[0],
+                                   self.betas[1], self.eps), adam_discard_grad=not self.store_grad)
+        else:
+            self.graph.propagate_mean_bwd_raw(self.g_final, self.K, self.inc, out=self.grad, accumulate=True, mask=slot.bitmap)
+            # grad += A . g_view (d view / d E0 = A for the first layer): live rows of g_view are the batch's unique
+            # users and positives, a subset of the bitmap (its other rows read zeros)
+            ops.spmm_ex_raw(self.graph, g_view, sum_in=self.grad, sum_out=self.grad, x_rows=slot.bitmap)
+            if adam_step > 0:
+                ops.adam_step_raw(self.params, self.grad, self.exp_avg, self.exp_avg_sq, self.lr, adam_step, self.betas[0],
+                                  self.betas[1], self.eps)
+
+    def _backward_plain(self, slot, loss, three, adam_step):
         mask = slot.bitmap
         if self.exchange is not None:
             mask = self.touched = self.exchange(slot, loss)
-        if _adam_step > 0 and slot.use_fields and not three and self.exchange is None:
+        if adam_step > 0 and slot.use_fields and not three and self.exchange is None:
             # g_final is non-zero on the batch's rows; step k's input lives on their (k - 1)-hop set
             self.graph.propagate_mean_bwd_adam_fields_raw(self.g_final, self.K, self.inc, self.grad, True,
                                                           slot.hops[: self.K - 1] + [None], self.params, self.exp_avg,
-                                                          self.exp_avg_sq, self.lr, _adam_step, self.betas[0],
+                                                          self.exp_avg_sq, self.lr, adam_step, self.betas[0],
                                                           self.betas[1], self.eps, discard_grad=not self.store_grad)
-        elif _adam_step > 0:
+        elif adam_step > 0:
             self.graph.propagate_mean_bwd_adam_raw(self.g_final, self.K, self.inc, self.grad, True, mask, self.params,
-                                                   self.exp_avg, self.exp_avg_sq, self.lr, _adam_step, self.betas[0],
+                                                   self.exp_avg, self.exp_avg_sq, self.lr, adam_step, self.betas[0],
                                                    self.betas[1], self.eps, discard_grad=not self.store_grad)
         else:
             self.graph.propagate_mean_bwd_raw(self.g_final, self.K, self.inc, out=self.grad, accumulate=True, mask=mask)
-        slot.free = slot.free_ev
-        slot.free.record(main.cuda_stream)
-        self._ends.append(slot.free)
-        self._final_version = -1
-        return loss
 
     # ---- one whole training step (loss_and_grad + dense Adam), for callers without a torch optimizer
     @torch.no_grad()
@@ -675,97 +741,6 @@ class PropagationEngine:
     def rating(self, users):
         fin = self.propagate()
         return ops.score_dense(fin[: self.U], fin[self.U:], users)
-
-
-class BatchPrep:
-    """The index-only work of a batch — the bitmap of its <= 3B panel rows, (optionally) the live work units of that bitmap
-    on a graph, the sorted scatter plan of its (row, slot) pairs — on a SIDE stream, one batch ahead of the step that uses
-    it: what PropagationEngine does for the LightGCN family, for engines with their own step (EgcfEngine / EgcfAltEngine, and
-    the PanelEngine subclasses NgcfEngine, GccfEngine, BigcfEngine).
-    Three slots: the batch being processed, the one prepared ahead, and one whose last step the host has seen complete.
-
-        prep.prefetch(users, pos, neg)            # the trainer's lookahead (optional)
-        slot = prep.take(users, pos, neg)         # the step: finds the prepared slot (or prepares now), orders the main
-        ...  slot.bitmap / slot.units / slot.ws   #   stream behind it
-        prep.release(slot)                        # after the last launch that reads them
-    """
-
-    class _Slot:
-        def __init__(self, words, device):
-            self.bitmap = torch.zeros(words, dtype=torch.int32, device=device)
-            self.units, self.ws, self.B = None, None, -1
-            self.done, self.free_ev, self.free = ops.LocalEvent(), ops.LocalEvent(), None
-            self.key, self.ids, self.stamp = None, None, 0
-
-    def __init__(self, num_users, n_rows, dim, device, units_graph=None, extra=None):
-        """extra(slot, users, pos, neg, raw_stream): more index-only work of the batch, enqueued on the side stream before the
-        slot's `done` event (EgcfEngine, BigcfEngine: plan_infonce, the id lists of their InfoNCE calls)."""
-        self.U, self.n, self.d, self.device, self.graph = int(num_users), int(n_rows), int(dim), device, units_graph
-        self.extra = extra
-        self._slots = [self._Slot((self.n + 31) // 32, device) for _ in range(3)]  # (three: see PropagationEngine's pacing)
-        self._ends = []
-        self._paced = os.environ.get("IDG_PACE", "1") != "0"
-        self._side = ops.side_stream(device)
-        self._side_raw = self._side.cuda_stream
-        self._fork = ops.LocalEvent()
-        self._id_storage, self._stamp = None, 0
-
-    def _prepare(self, slot, users, pos, neg):
-        main = torch.cuda.current_stream()
-        B = int(users.shape[0])
-        fresh = slot.B != B  # workspaces (re)allocated on main, first written on the side stream: order it behind main once
-        if fresh:
-            slot.ws, slot.units, slot.B = ops.bpr_workspace(B, self.d, self.device), None, B
-        if slot.free is not None:
-            slot.free.wait(self._side_raw)  # the step that last used this slot has consumed it
-        # the side stream must not read the ids before the main stream has produced them: once per storage (batches are
-        # slices of one epoch-long tensor), as PropagationEngine._prepare does
-        src = (users.untyped_storage().data_ptr(), pos.untyped_storage().data_ptr(), neg.untyped_storage().data_ptr())
-        if slot.free is None or src != self._id_storage or fresh:
-            self._id_storage = src
-            self._fork.record(main.cuda_stream)
-            self._fork.wait(self._side_raw)
-        ops.bpr_touch_rows_raw(users, pos, neg, self.U, slot.bitmap, stream=self._side_raw, clear_bits=self.n)
-        if self.graph is not None:
-            slot.units = self.graph.live_units(slot.bitmap, 3 * B, ws=slot.units, stream=self._side_raw)
-        ops.bpr_plan_raw(users, pos, neg, self.U, self.n, self.d, ws=slot.ws, stream=self._side_raw)
-        if self.extra is not None:
-            self.extra(slot, users, pos, neg, self._side_raw)
-        slot.done.record(self._side_raw)
-        slot.key = (users.data_ptr(), pos.data_ptr(), neg.data_ptr(), B)
-        slot.ids = (users, pos, neg)  # alive until the side stream has read them
-
-    def _next(self):
-        free = [sl for sl in self._slots if sl.key is None]
-        slot = min(free if free else self._slots, key=lambda sl: sl.stamp)
-        self._stamp += 1
-        slot.stamp = self._stamp
-        return slot
-
-    def prefetch(self, users, pos, neg):
-        self._prepare(self._next(), users, pos, neg)
-
-    def take(self, users, pos, neg):
-        key = (users.data_ptr(), pos.data_ptr(), neg.data_ptr(), int(users.shape[0]))
-        slot = next((sl for sl in self._slots if sl.key == key), None)
-        ahead = slot is not None
-        if slot is None:
-            slot = self._next()
-            self._prepare(slot, users, pos, neg)
-        slot.key = None
-        # the host stays at most two steps ahead of the device; a batch prepared ahead is then known to be ready when its
-        # step is enqueued, and the step's stream needs no wait (PropagationEngine.loss_and_grad: 4.5 us per barrier packet)
-        if self._paced and len(self._ends) >= 2:
-            self._ends[-2].synchronize()
-        del self._ends[:-2]  # (also when not paced)
-        if not (ahead and self._paced and slot.done.query()):
-            slot.done.wait(torch.cuda.current_stream().cuda_stream)
-        return slot
-
-    def release(self, slot):
-        slot.free = slot.free_ev
-        slot.free.record(torch.cuda.current_stream().cuda_stream)
-        self._ends.append(slot.free)
 
 
 def plan_infonce(slot, users, pos, num_users, n_rows, dim, device, stream):

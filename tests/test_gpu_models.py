@@ -1035,21 +1035,27 @@ def test_egcf_trainer_loop_runs(mode, tmp_path, golden_small):
     assert len(losses_) == 2 and losses_[1] < losses_[0]
 
 
-@pytest.mark.parametrize("mname", ["EGCF", "EGCF:alternating", "NGCF", "LightGCN", "SimGCL", "XSimGCL", "MFBPR"])
+@pytest.mark.parametrize("mname", ["EGCF", "EGCF:alternating", "NGCF", "LightGCN", "SimGCL", "XSimGCL", "MFBPR", "SGL",
+                                   "DirectAU@LightGCN", "DirectAU@MF", "SCCF@LightGCN", "SCCF@MF", "LightCCF@LightGCN",
+                                   "LightCCF@MF", "LightCSCF@LightGCN", "LightCSCF@MF"])
 def test_batch_lookahead_changes_nothing(mname, tmp_path, golden_small):
-    """The side-stream preparation of the NEXT batch (engine.BatchPrep / PropagationEngine._prepare: row bitmap, live units,
-    scatter plan, the id lists of the step's InfoNCE calls — called by the trainer through prefetch_batch) is index-only
+    """The side-stream preparation of the NEXT batch (engine.BatchPrep._prepare and the engines' _index_work: row bitmap, live
+    units, scatter plan, the id lists of the step's InfoNCE calls — called by the trainer through prefetch_batch) is index-only
     work: four steps over four different batches with the lookahead equal, bit for bit, the same steps without it — losses
     and every parameter.  (With the lookahead the step's stream takes no event wait at all once the host can see the
-    preparation complete; without it the batch is prepared inside the step and waited for: both orders of the two streams.)"""
+    preparation complete; without it the batch is prepared inside the step and waited for: both orders of the two streams.)
+    "Name:mode" / "Name@encoder" set that configuration key; SGL steps through fused_sgl_step on one pair of edge-dropped
+    views per run (the same pair in both: the draw is seeded)."""
     import importlib
+    import random
 
     import utility.utility_function.tools as tools
     from idgrec_amd import ops
 
+    mname, _, encoder = mname.partition("@")
     mname, _, mode = mname.partition(":")
-    cls = getattr(importlib.import_module("models." + mname), mname)
-    cfg = _cfg(mname, **({"mode": mode} if mode else {}))
+    module = importlib.import_module("models." + mname)
+    cfg = _cfg(mname, **({"mode": mode} if mode else {}), **({"encoder": encoder} if encoder else {}))
     data = _data_with(tmp_path, golden_small, cfg)
     gen = torch.Generator().manual_seed(7)
     B, steps = 192, 4
@@ -1060,7 +1066,13 @@ def test_batch_lookahead_changes_nothing(mname, tmp_path, golden_small):
     runs = []
     for ahead in (False, True):
         tools.set_seed(2024)
-        m = cls(cfg, data, torch.device("cuda")).to("cuda")
+        if mname == "SGL":
+            trainer = module.Trainer(None, cfg, data, torch.device("cuda"), None)
+            m = trainer.model.to("cuda")
+            random.seed(2024)  # (the views are drawn from Python's own stream, which tools.set_seed leaves alone)
+            views = trainer._views()
+        else:
+            m = getattr(module, mname)(cfg, data, torch.device("cuda")).to("cuda")
         assert m.fused_step_available()
         opt = ops.Adam(list(m.parameters()), lr=float(cfg["learn_rate"]))
         ops.reset_noise_stream()
@@ -1070,7 +1082,10 @@ def test_batch_lookahead_changes_nothing(mname, tmp_path, golden_small):
         for s in range(steps):
             if ahead and s + 1 < steps:
                 m.prefetch_batch(*batches[s + 1])
-            assert m.fused_train_step(*batches[s], out[s], opt)
+            if mname == "SGL":
+                assert m.fused_sgl_step(*batches[s], *views, out[s], opt)
+            else:
+                assert m.fused_train_step(*batches[s], out[s], opt)
         torch.cuda.synchronize()
         runs.append((out.cpu(), {k: v.detach().cpu().clone() for k, v in m.named_parameters()}))
     assert torch.isfinite(runs[0][0]).all() and torch.equal(runs[0][0], runs[1][0])
