@@ -5,7 +5,7 @@ sequence (models/LightGCN.py:54-72 + utility/utility_train/trainer.py:42-56)
 
 as a fixed chain of C-ABI calls on preallocated device buffers — no autograd graph, no
 temporaries, no host synchronisation.  Numerically it is the same chain the autograd
-operators in ops.py execute (tests compare the two), so models may use either.
+operators in ops/ execute (tests compare the two), so models may use either.
 
 Embedding layout: ONE [num_users + num_items, d] panel, users first; the model's two
 nn.Embedding weights are views into it (no torch.cat per step).

@@ -1,14 +1,6 @@
-"""Device operators: torch tensors in, torch tensors out, computed by libidgrec.so's HIP
-kernels through the C ABI.  PyTorch only supplies device memory, streams and autograd
-bookkeeping.  Every operator requires CUDA(=HIP) tensors; there is no CPU implementation —
-calling one with CPU tensors raises.
-
-Operator boundary: `spmm(graph, X)` stands where the reference calls
-`torch.sparse.mm(self.Graph, X)` (models/LightGCN.py:44); `propagate_mean` is the whole
-`aggregate()` loop (models/LightGCN.py:36-52); `bpr_loss` is the gather + get_bpr_loss +
-reg_lambda*get_reg_loss of `forward()` (models/LightGCN.py:57-68); `score_topk` is
-get_rating_for_test + mask + torch.topk (utility/utility_train/batch_test.py:59-68).
-"""
+"""csrc/idg_graph.hip — Graph, the products with their epilogues, the row movers, the noise streams, the propagation operators —
+and, each under its section header, the families every encoder builds on: InfoNCE (idg_ssl), row normalisation, BPR, the
+thin dense layer and NGCF, LR-GCCF, GCMC, IMP-GCN's groups, BIGCF's intent layer, HCCF's hypergraph layer."""
 import ctypes as C
 import os
 import weakref
@@ -16,52 +8,9 @@ import weakref
 import numpy as np
 import torch
 
-from . import native
-from .native import check, lib
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream():
-    """The current HIP stream of the current device as a raw handle.  torch.cuda.current_stream() builds a Stream
-    object through several Python layers (~8 us): with ~40 launches per sharded step that alone made the host
-    the bottleneck, so the raw accessor is used when this torch has it."""
-    if _raw_stream is not None:
-        return _raw_stream(torch._C._cuda_getDevice())
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _require_device(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(
-                "idgrec_amd operators run on MI355X only: got a %s tensor. There is no CPU fallback; "
-                "move the model and inputs to the GPU (device='cuda')." % t.device)
-
-
-def _require_ids(*tensors):
-    """The raw entry points read ids as contiguous int64 (the reference's batches, trainer.py:27-29): anything else
-    would be read past its end."""
-    for t in tensors:
-        if t.dtype != torch.int64 or not t.is_contiguous():
-            raise TypeError("batch ids must be contiguous int64 tensors (got %s, contiguous=%s)" % (t.dtype, t.is_contiguous()))
-
-
-def _f32c(t, name):
-    if t.dtype != torch.float32:
-        raise TypeError("%s must be float32 (got %s)" % (name, t.dtype))
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _i64c(t, name):
-    if t.dtype != torch.int64:
-        t = t.long()
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None  # ctypes converts int / None for void* parameters
+from .. import native
+from ..native import check, lib
+from ._base import _cached_ws, _f32c, _i64c, _ld, _ptr, _require_device, _require_ids, _row_base, _stream
 
 
 def _forget_units_ws(ws_ptr):
@@ -287,14 +236,8 @@ class Graph:
         return rows, seg, chunk
 
     def _workspace(self, kind, d):
-        key = (kind, int(d))
-        ws = self._ws.get(key)
-        if ws is None:
-            fn = lib.idg_spmm_workspace_bytes if kind == "spmm" else lib.idg_propagate_workspace_bytes
-            nbytes = int(fn(self._h, int(d)))
-            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
-            self._ws[key] = ws
-        return ws
+        fn = lib.idg_spmm_workspace_bytes if kind == "spmm" else lib.idg_propagate_workspace_bytes
+        return _cached_ws(self._ws, (kind, int(d)), lambda: max(int(fn(self._h, int(d))), 16), self.device)
 
     # ---- raw (non-autograd) calls
     def spmm_raw(self, X, addend=None, out=None):
@@ -515,10 +458,7 @@ def infonce_cross_raw(view, users, items, num_users, temperature, g=None, loss=N
     if loss is None:
         loss = torch.zeros(2, dtype=torch.float32, device=view.device)
     if ws is None:
-        key = (n, B, d, view.device)
-        ws = _ssl_ws.get(key)
-        if ws is None:
-            ws = _ssl_ws[key] = torch.empty(int(lib.idg_infonce_workspace_bytes(n, B, d)), dtype=torch.uint8, device=view.device)
+        ws = _cached_ws(_ssl_ws, (n, B, d, view.device), lambda: lib.idg_infonce_workspace_bytes(n, B, d), view.device)
     check(lib.idg_infonce_cross_ex_f32(_ptr(view), n, d, _ptr(users), _ptr(items), B, int(num_users), float(temperature), _ptr(loss),
                                        _ptr(g), float(grad_scale), int(bool(planned)), _ptr(ws), _stream()), "idg_infonce_cross_f32")
     return loss, ws
@@ -700,11 +640,8 @@ def propagate_views_raw(graph, E0, K, include_layer0, eps, streams, outs, out_ro
         # one C call: shared first product, per-view perturbation, and (with out_rows) ONE multi-panel launch for the
         # last layer of all passes — same values as the composition below
         n_views = len(streams)
-        key = ("views", d, n_views)
-        ws = graph._ws.get(key)
-        if ws is None:
-            ws = graph._ws[key] = torch.empty(int(lib.idg_propagate_views_workspace_bytes(graph._h, d, n_views)),
-                                              dtype=torch.uint8, device=E0.device)
+        ws = _cached_ws(graph._ws, ("views", d, n_views), lambda: lib.idg_propagate_views_workspace_bytes(graph._h, d, n_views),
+                        E0.device)
         seeds = (C.c_uint64 * n_views)(*[int(sd) for sd, _ in streams])
         sids = (C.c_uint64 * n_views)(*[int(si) for _, si in streams])
         views = (C.c_void_p * n_views)(*[o.data_ptr() for o in outs[1:]])
@@ -913,57 +850,6 @@ def propagate_normalized(graph, E0, K, gamma):
 _bpr_ws_cache = {}
 
 
-class LocalEvent:
-    """A device-local event (idg_event_*): orders two streams of one device without the system-scope fence of a default
-    HIP / torch event (see include/idgrec.h).  record / wait take raw stream handles (torch.cuda.Stream.cuda_stream)."""
-
-    __slots__ = ("_h", "_done")
-
-    def __init__(self):
-        import ctypes as C
-
-        h = C.c_void_p()
-        check(lib.idg_event_create(C.byref(h)), "idg_event_create")
-        self._h, self._done = h, C.c_int(0)
-
-    def record(self, stream):
-        check(lib.idg_event_record(self._h, stream), "idg_event_record")
-
-    def wait(self, stream):
-        """Make `stream` wait for the recorded work."""
-        check(lib.idg_stream_wait_event(stream, self._h), "idg_stream_wait_event")
-
-    def synchronize(self):
-        """Block the host until the recorded work has completed."""
-        check(lib.idg_event_synchronize(self._h), "idg_event_synchronize")
-
-    def query(self):
-        import ctypes as C
-
-        check(lib.idg_event_query(self._h, C.byref(self._done)), "idg_event_query")
-        return bool(self._done.value)
-
-    def __del__(self):
-        try:
-            lib.idg_event_destroy(self._h)
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-
-def side_stream(device):
-    """A second stream for index-only work, bound to a hardware queue NOW.  HIP multiplexes a process's streams over a
-    few hardware queues, binding each at its first use; a side stream first used after other streams have taken theirs
-    (a communicator's) can land on the MAIN stream's queue, and its kernels then serialise with the step's (measured:
-    +30 us per step).  Engines therefore create theirs at construction — before any communicator exists — and touch it
-    once.  (A high-priority stream would have a queue class of its own, but waits between the two classes cost far
-    more than they save: measured 0.33 -> 0.91 ms per step.)"""
-    s = torch.cuda.Stream(device=device)
-    with torch.cuda.stream(s):
-        torch.zeros(1, dtype=torch.int32, device=device)
-    s.synchronize()
-    return s
-
-
 def bpr_workspace(B, d, device):
     """A private BPR scratch buffer (callers that pipeline batches keep one per in-flight batch)."""
     return torch.empty(int(lib.idg_bpr_workspace_bytes(int(B), int(d))), dtype=torch.uint8, device=device)
@@ -973,12 +859,7 @@ def _bpr_ws(B, d, device):
     """Scratch of the fused BPR calls.  One buffer per (batch size, width, device): the forward and
     backward calls of a step (and the side-stream plan) must see the SAME buffer.  Callers that run
     two BPR steps concurrently on different streams need their own workspace (not done here)."""
-    key = (int(B), int(d), device)
-    ws = _bpr_ws_cache.get(key)
-    if ws is None:
-        ws = torch.empty(int(lib.idg_bpr_workspace_bytes(int(B), int(d))), dtype=torch.uint8, device=device)
-        _bpr_ws_cache[key] = ws
-    return ws
+    return _cached_ws(_bpr_ws_cache, (int(B), int(d), device), lambda: lib.idg_bpr_workspace_bytes(int(B), int(d)), device)
 
 
 class _BprLoss(torch.autograd.Function):
@@ -1146,10 +1027,7 @@ def linear_wgrad_raw(X, G, out=None, accumulate=False):
         raise ValueError("linear_wgrad_raw: X and G must have the same number of rows")
     if out is None:
         out = torch.empty((d1, d2), dtype=torch.float32, device=X.device)
-    key = (n, d1, d2, X.device)
-    ws = _wgrad_ws.get(key)
-    if ws is None:
-        ws = _wgrad_ws[key] = torch.empty(int(lib.idg_linear_wgrad_workspace_bytes(n, d1, d2)), dtype=torch.uint8, device=X.device)
+    ws = _cached_ws(_wgrad_ws, (n, d1, d2, X.device), lambda: lib.idg_linear_wgrad_workspace_bytes(n, d1, d2), X.device)
     check(lib.idg_linear_wgrad_f32(_ptr(X), d1, _ptr(G), d2, n, d1, d2, _ptr(out), int(bool(accumulate)), _ptr(ws), _stream()),
           "idg_linear_wgrad_f32")
     return out
@@ -1165,9 +1043,7 @@ def colsum_raw(X, out=None, accumulate=False):
     n, d = X.shape
     if out is None:
         out = torch.empty(d, dtype=torch.float32, device=X.device)
-    ws = _colsum_ws.get((d, X.device))
-    if ws is None:
-        ws = _colsum_ws[(d, X.device)] = torch.empty(int(lib.idg_colsum_workspace_bytes(d)), dtype=torch.uint8, device=X.device)
+    ws = _cached_ws(_colsum_ws, (d, X.device), lambda: lib.idg_colsum_workspace_bytes(d), X.device)
     check(lib.idg_colsum_f32(_ptr(X), d, n, d, _ptr(out), int(bool(accumulate)), _ptr(ws), _stream()), "idg_colsum_f32")
     return out
 
@@ -1236,8 +1112,6 @@ class _NgcfTransform(torch.autograd.Function):
 def ngcf_transform(side, ego, W1, W2):
     """torch.matmul(side, W1) + torch.matmul(ego * side, W2) (models/NGCF.py:88-99, biases left to ngcf_layer_tail).
     MFMA kernel when the widths allow it (d1 % 64 == 0 and d2 % 64 == 0), the two thin GEMMs otherwise."""
-    import os
-
     d1, d2 = W1.shape
     if d1 % 64 == 0 and d2 % 64 == 0 and side.is_cuda and os.environ.get("IDG_NGCF_MFMA", "1") != "0":
         return _NgcfTransform.apply(side, ego, W1, W2)
@@ -1303,10 +1177,7 @@ def gccf_layer_bwd_raw(gE, gN, ldgn, gn_rows, side, W, p, seed, stream_id, g_sid
     w_grads = [side^T . gT | column sums of gT].  gN is read `gn_slot` floats into each row, leading dimension ldgn."""
     _require_device(gE, gN, gn_rows, side, W, g_side, w_grads)
     n, d = side.shape
-    ws = _gccf_ws.get((d, side.device))
-    if ws is None:
-        ws = _gccf_ws[(d, side.device)] = torch.empty(max(int(lib.idg_gccf_layer_bwd_workspace_bytes(d)), 16), dtype=torch.uint8,
-                                                      device=side.device)
+    ws = _cached_ws(_gccf_ws, (d, side.device), lambda: max(int(lib.idg_gccf_layer_bwd_workspace_bytes(d)), 16), side.device)
     check(lib.idg_gccf_layer_bwd_f32(_ptr(gE), None if gN is None else gN.data_ptr() + 4 * int(gn_slot), int(ldgn), _ptr(gn_rows),
                                      _ptr(side), _ptr(W), n, d, float(p), C.c_uint64(seed), C.c_uint64(stream_id), _ptr(g_side),
                                      _ptr(w_grads), _ptr(ws), _stream()), "idg_gccf_layer_bwd_f32")
@@ -1384,10 +1255,7 @@ def gcmc_layer_bwd_raw(T, gE, gN, ldgn, gn_rows, side, Wg, bg, Wm, p, seed, stre
     floats into each row, leading dimension ldgn."""
     _require_device(T, gE, gN, gn_rows, side, Wg, bg, Wm, g_side, w_grads)
     n, d = side.shape
-    ws = _gcmc_ws.get((d, side.device))
-    if ws is None:
-        ws = _gcmc_ws[(d, side.device)] = torch.empty(max(int(lib.idg_gcmc_layer_bwd_workspace_bytes(d)), 16), dtype=torch.uint8,
-                                                      device=side.device)
+    ws = _cached_ws(_gcmc_ws, (d, side.device), lambda: max(int(lib.idg_gcmc_layer_bwd_workspace_bytes(d)), 16), side.device)
     check(lib.idg_gcmc_layer_bwd_f32(_ptr(T), _ptr(gE), None if gN is None else gN.data_ptr() + 4 * int(gn_slot), int(ldgn),
                                      _ptr(gn_rows), _ptr(side), _ptr(Wg), _ptr(bg), _ptr(Wm), n, d, float(slope), float(p),
                                      C.c_uint64(seed), C.c_uint64(stream_id), _ptr(g_side), _ptr(w_grads), _ptr(ws), _stream()),
@@ -1502,10 +1370,7 @@ class GroupCsr:
     def workspace(self, G):
         if not self.n_long:
             return None
-        ws = self._ws.get(G)
-        if ws is None:
-            ws = self._ws[G] = torch.empty(int(lib.idg_grouped_spmm_workspace_bytes(self.n_chunks, G)), dtype=torch.uint8, device=self.device)
-        return ws
+        return _cached_ws(self._ws, G, lambda: lib.idg_grouped_spmm_workspace_bytes(self.n_chunks, G), self.device)
 
 
 def _check_groups(who, G):
@@ -1702,15 +1567,6 @@ def grouped_propagate(csr, E0, member, n_products, groups, summed=False):
 _intent_ws = {}
 
 
-def _ld(t):
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
-
-
-def _row_base(t, base_row):
-    """Pointer of GLOBAL row 0 of a panel whose first row is global row base_row (never dereferenced below that row)."""
-    return None if t is None else t.data_ptr() - 4 * int(base_row) * _ld(t)
-
-
 def intent_noise_raw(out, seed, stream_id, base_row=0):
     """idg_intent_noise_f32: out[r, f] = the normal of (seed, stream_id, base_row + r, f) — the Z the intent kernels generate,
     at any width (the composed path of intent_mix draws it here)."""
@@ -1743,10 +1599,7 @@ def intent_bwd_raw(gF, gT_in, rows_bitmap, X, W, gX, gW, row0=0, nrows=None, noi
     d, k = W.shape
     nrows = X.shape[0] - (int(row0) - int(base_row)) if nrows is None else nrows
     if ws is None:
-        ws = _intent_ws.get((d, k, X.device))
-        if ws is None:
-            ws = _intent_ws[(d, k, X.device)] = torch.empty(max(int(lib.idg_intent_bwd_workspace_bytes(d, k)), 16), dtype=torch.uint8,
-                                                           device=X.device)
+        ws = _cached_ws(_intent_ws, (d, k, X.device), lambda: max(int(lib.idg_intent_bwd_workspace_bytes(d, k)), 16), X.device)
     check(lib.idg_intent_bwd_f32(_row_base(gF, base_row), _ld(gF), _row_base(gT_in, base_row), 0 if gT_in is None else _ld(gT_in),
                                  _ptr(gt_rows), _ptr(rows_bitmap), _row_base(X, base_row), _ld(X), int(row0), int(nrows), _ptr(W), d, k,
                                  _row_base(noise, base_row), C.c_uint64(seed), C.c_uint64(stream_id), _row_base(gX, base_row), _ld(gX),
@@ -1815,11 +1668,8 @@ _hyper_ws = {}
 
 
 def _hyper_workspace(device, d=64, h=64):
-    ws = _hyper_ws.get((d, h, device))
-    if ws is None:
-        nbytes = max(int(lib.idg_hyper_latent_workspace_bytes(d, h)), int(lib.idg_hyper_close_workspace_bytes(d, h)), 16)
-        ws = _hyper_ws[(d, h, device)] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws
+    return _cached_ws(_hyper_ws, (d, h, device), lambda: max(int(lib.idg_hyper_latent_workspace_bytes(d, h)),
+                                                             int(lib.idg_hyper_close_workspace_bytes(d, h)), 16), device)
 
 
 def _mask_base(mask, base_row):
@@ -1966,10 +1816,7 @@ def infonce_pair_raw(view1, view2, users, items, num_users, temperature, g1=None
     if ws is None:
         if planned:
             raise ValueError("infonce_pair_raw: planned=True needs the workspace idg_infonce_plan wrote into")
-        key = (n, B, d, view1.device)
-        ws = _ssl_ws.get(key)
-        if ws is None:
-            ws = _ssl_ws[key] = infonce_workspace(n, B, d, view1.device)
+        ws = _cached_ws(_ssl_ws, (n, B, d, view1.device), lambda: lib.idg_infonce_workspace_bytes(n, B, d), view1.device)
     if loss is None:
         loss = torch.empty(2, dtype=torch.float32, device=view1.device)
     check(lib.idg_infonce_pair_f32(_ptr(view1), _ptr(view2), n, d, _ptr(users), _ptr(items), B, int(num_users),
@@ -2002,990 +1849,6 @@ def infonce_pair(view1, view2, users, items, num_users, temperature, dedup=True)
     — the self-supervised term of SimGCL / XSimGCL (models/SimGCL.py:79-84) — as one differentiable operator on
     the two [n, d] view panels (users first).  dedup=False: the id lists as they are, duplicates included (SGL)."""
     return _InfoNCEPair.apply(view1, view2, users, items, num_users, temperature, bool(dedup))
-
-
-# ----------------------------------------------------------------------------------- DirectAU: alignment + uniformity
-_au_ws_cache = {}
-
-
-def align_uniform_workspace(B, d, device):
-    """A private idg_align_uniform_f32 scratch buffer (O(B d): the pair matrix is never stored)."""
-    return torch.empty(int(lib.idg_align_uniform_workspace_bytes(int(B), int(d))), dtype=torch.uint8, device=device)
-
-
-def align_uniform_raw(final_panel, ego_panel, users, pos, num_users, gamma, reg_lambda, g_final=None, g_ego=None,
-                      loss=None, upstream=None, accumulate=True, plan_ws=None, ws=None):
-    """idg_align_uniform_f32: loss[3] = [align, gamma * uniform, reg_lambda * reg] of DirectAU (models/DirectAU.py:59-79)
-    over the batch's rows users / num_users + pos of final_panel (reg over the same rows of ego_panel).
-    g_final / g_ego (optional): d(align + gamma * uniform) / d final and d(reg) / d ego — the same tensor for the MF
-    encoder (final_panel is ego_panel) — each scaled by `upstream` (device [3], d total / d loss[k]; None = ones).
-    accumulate=True adds into the rows the batch touches; False STORES them (the rows of
-    bpr_touch_rows_raw(users, pos, pos)), nothing else is written.  plan_ws: a BPR workspace holding
-    bpr_plan_raw(users, pos, pos, ...) of this batch (index-only, prepared ahead on a side stream); None: in-call."""
-    _require_device(final_panel, ego_panel, users, pos, g_final, g_ego, loss, upstream)
-    _require_ids(users, pos)
-    n, d = final_panel.shape
-    B = users.shape[0]
-    if pos.shape[0] != B or ego_panel.shape != final_panel.shape:
-        raise ValueError("align_uniform_raw: id lists / panels of different shapes")
-    if ws is None:
-        key = (int(B), int(d), final_panel.device)
-        ws = _au_ws_cache.get(key)
-        if ws is None:
-            ws = _au_ws_cache[key] = align_uniform_workspace(B, d, final_panel.device)
-    if loss is None:
-        loss = torch.empty(3, dtype=torch.float32, device=final_panel.device)
-    check(lib.idg_align_uniform_f32(_ptr(final_panel), _ptr(ego_panel), n, d, _ptr(users), _ptr(pos), B, int(num_users),
-                                    float(gamma), float(reg_lambda), _ptr(loss), _ptr(upstream), _ptr(g_final), _ptr(g_ego),
-                                    int(bool(accumulate)), _ptr(plan_ws), _ptr(ws), _stream()),
-          "idg_align_uniform_f32")
-    return loss
-
-
-class _AlignUniform(torch.autograd.Function):
-    """The forward computes the losses only; the backward runs the call again with the three incoming gradient
-    scalars (the pair pass twice — this is the path of widths the fused step does not cover)."""
-
-    @staticmethod
-    def forward(ctx, final_panel, ego_panel, users, pos, num_users, gamma, reg_lambda):
-        _require_device(final_panel, ego_panel, users, pos)
-        fin = _f32c(final_panel.detach(), "final_panel")
-        same = ego_panel is final_panel
-        ego = fin if same else _f32c(ego_panel.detach(), "ego_panel")
-        users, pos = _i64c(users, "users"), _i64c(pos, "pos")
-        loss = align_uniform_raw(fin, ego, users, pos, num_users, gamma, reg_lambda)
-        ctx.save_for_backward(fin, ego, users, pos)
-        ctx.meta = (int(num_users), float(gamma), float(reg_lambda), same)
-        return loss[0], loss[1], loss[2]
-
-    @staticmethod
-    def backward(ctx, g_align, g_unif, g_reg):
-        fin, ego, users, pos = ctx.saved_tensors
-        num_users, gamma, reg_lambda, same = ctx.meta
-        up = torch.stack([g.to(torch.float32).reshape(()) for g in (g_align, g_unif, g_reg)]).contiguous()
-        g_final = torch.zeros_like(fin)
-        g_ego = g_final if same else torch.zeros_like(ego)
-        align_uniform_raw(fin, fin if same else ego, users, pos, num_users, gamma, reg_lambda, g_final, g_ego,
-                          upstream=up, accumulate=True)
-        return g_final, (None if same else g_ego), None, None, None, None, None
-
-
-class _AlignUniformSame(torch.autograd.Function):
-    """final == ego (the MF encoder): one differentiable input that receives both gradients."""
-
-    @staticmethod
-    def forward(ctx, panel, users, pos, num_users, gamma, reg_lambda):
-        return _AlignUniform.forward(ctx, panel, panel, users, pos, num_users, gamma, reg_lambda)
-
-    @staticmethod
-    def backward(ctx, g_align, g_unif, g_reg):
-        return (_AlignUniform.backward(ctx, g_align, g_unif, g_reg)[0], None, None, None, None, None)
-
-
-def align_uniform_loss(final_panel, ego_panel, users, pos, num_users, gamma, reg_lambda):
-    """DirectAU's loss triple (align, gamma * uniform, reg_lambda * reg) as 0-d tensors, differentiable w.r.t. both
-    [num_users + num_items, d] panels: get_align_loss(a, b), gamma * (get_uniform_loss(a) + get_uniform_loss(b)) / 2 and
-    reg_lambda * get_reg_loss(ego rows) with a = final[users], b = final[num_users + pos] (models/DirectAU.py:59-79).
-    Passing the same tensor twice is the MF encoder."""
-    if ego_panel is final_panel:
-        return _AlignUniformSame.apply(final_panel, users, pos, num_users, gamma, reg_lambda)
-    return _AlignUniform.apply(final_panel, ego_panel, users, pos, num_users, gamma, reg_lambda)
-
-
-# ----------------------------------------------------------------------------------- SCCF: second-order in-batch contrast
-_sccf_ws_cache = {}
-
-
-def sccf_workspace(B, d, device):
-    """A private idg_sccf_loss_f32 scratch buffer (the padded operands, the per-tile partial gradient rows, the plan)."""
-    size = int(lib.idg_sccf_workspace_bytes(int(B), int(d)))
-    if size == 0:
-        raise ValueError("sccf_workspace: B = %d, d = %d is not built (1 <= d <= 256, 1 <= B < 2^22)" % (B, d))
-    return torch.empty(size, dtype=torch.uint8, device=device)
-
-
-def sccf_loss_raw(final, users, pos, num_users, temperature, g_final=None, g_ego=None, loss=None, upstream=None,
-                  accumulate=True, plan_ws=None, ws=None):
-    """idg_sccf_loss_f32: loss[2] = [-up, down] of SCCF (models/SCCF.py:54-81) over the batch's rows users / num_users + pos
-    of `final`.  g_final (optional): d(up[0] loss[0] + up[1] loss[1]) / d final with `upstream` = up (device [2]; None =
-    ones); accumulate=True adds into the rows the batch touches, False STORES them (the rows of
-    bpr_touch_rows_raw(users, pos, pos)) and, given g_ego (a second panel, never g_final), stores zeros to its same rows.
-    plan_ws: a BPR workspace holding bpr_plan_raw(users, pos, pos, ...) of this batch; None: in-call."""
-    _require_device(final, users, pos, g_final, g_ego, loss, upstream)
-    _require_ids(users, pos)
-    n, d = final.shape
-    B = users.shape[0]
-    if pos.shape[0] != B:
-        raise ValueError("sccf_loss_raw: id lists of different lengths")
-    if ws is None:
-        key = (int(B), int(d), final.device)
-        ws = _sccf_ws_cache.get(key)
-        if ws is None:
-            ws = _sccf_ws_cache[key] = sccf_workspace(B, d, final.device)
-    if loss is None:
-        loss = torch.empty(2, dtype=torch.float32, device=final.device)
-    check(lib.idg_sccf_loss_f32(_ptr(final), n, d, _ptr(users), _ptr(pos), B, int(num_users), float(temperature), _ptr(loss),
-                                _ptr(upstream), _ptr(g_final), _ptr(g_ego), int(bool(accumulate)), _ptr(plan_ws), _ptr(ws),
-                                _stream()),
-          "idg_sccf_loss_f32")
-    return loss
-
-
-class _SCCFLoss(torch.autograd.Function):
-    """The forward computes the two losses only; the backward runs the call again with the incoming pair as upstream."""
-
-    @staticmethod
-    def forward(ctx, final, users, pos, num_users, temperature):
-        _require_device(final, users, pos)
-        fin = _f32c(final.detach(), "final")
-        users, pos = _i64c(users, "users"), _i64c(pos, "pos")
-        loss = sccf_loss_raw(fin, users, pos, num_users, temperature)
-        ctx.save_for_backward(fin, users, pos)
-        ctx.meta = (int(num_users), float(temperature))
-        return loss[0], loss[1]
-
-    @staticmethod
-    def backward(ctx, g_up, g_down):
-        fin, users, pos = ctx.saved_tensors
-        num_users, temperature = ctx.meta
-        up = torch.stack([g.to(torch.float32).reshape(()) for g in (g_up, g_down)]).contiguous()
-        g_final = torch.zeros_like(fin)
-        sccf_loss_raw(fin, users, pos, num_users, temperature, g_final, upstream=up, accumulate=True)
-        return g_final, None, None, None, None
-
-
-def sccf_loss(final, user, positive, num_users, temperature):
-    """SCCF's loss pair (neg_up, down) as 0-d tensors, differentiable w.r.t. the [num_users + num_items, d] panel:
-    neg_up = -mean_i log f(a_i.b_i), down = log(mean over distinct users x distinct positives of f(a_k.b_l) cu_k ci_l),
-    f(s) = exp(s / T) + exp(s^2 / T), a / b the normalised rows (models/SCCF.py:54-81)."""
-    return _SCCFLoss.apply(final, user, positive, num_users, temperature)
-
-
-# ----------------------------------------------------------------------------------- LightCCF / LightCSCF (idg_nance.hip)
-_na_ws_cache = {}
-
-
-def na_nce_workspace(B, d, device):
-    """A private idg_na_nce_f32 / idg_reg_rows_f32 scratch buffer (the padded operands, the per-tile partials, the plan)."""
-    size = int(lib.idg_na_nce_workspace_bytes(int(B), int(d)))
-    if size == 0:
-        raise ValueError("na_nce_workspace: B = %d, d = %d is not built (1 <= d <= 256, 1 <= B < 2^22)" % (B, d))
-    return torch.empty(size, dtype=torch.uint8, device=device)
-
-
-def _na_ws(B, d, device):
-    key = (int(B), int(d), device)
-    ws = _na_ws_cache.get(key)
-    if ws is None:
-        ws = _na_ws_cache[key] = na_nce_workspace(B, d, device)
-    return ws
-
-
-def na_nce_loss_raw(final, users, pos, num_users, temperature, margin=None, grad_scale=1.0, g_final=None, loss=None,
-                    upstream=None, accumulate=True, plan_ws=None, ws=None):
-    """idg_na_nce_f32: loss[1] = grad_scale * mean_i -log(f(a_i.b_i) / sum_j f(a_i.(a_j + b_j)) + 1e-5) over the batch's
-    rows users / num_users + pos of `final` (models/LightCCF.py:81-94; with margin = lambda_margin, models/LightCSCF.py:93-104;
-    margin None: LightCCF's f).  g_final (optional): upstream * d loss / d final (upstream: device [1]; None = 1);
-    accumulate=True adds into the rows the batch touches, False STORES every row of the plan.  plan_ws: a BPR workspace
-    holding bpr_plan_raw(users, pos, neg or pos, ...) of this batch; None: in-call."""
-    _require_device(final, users, pos, g_final, loss, upstream)
-    _require_ids(users, pos)
-    n, d = final.shape
-    B = users.shape[0]
-    if pos.shape[0] != B:
-        raise ValueError("na_nce_loss_raw: id lists of different lengths")
-    if margin is not None and not 0.0 <= float(margin) <= 2.0:
-        raise ValueError("na_nce_loss_raw: margin must be in [0, 2] (None: LightCCF's form), got %r" % (margin,))
-    if ws is None:
-        ws = _na_ws(B, d, final.device)
-    if loss is None:
-        loss = torch.empty(1, dtype=torch.float32, device=final.device)
-    check(lib.idg_na_nce_f32(_ptr(final), n, d, _ptr(users), _ptr(pos), B, int(num_users), float(temperature),
-                             -1.0 if margin is None else float(margin), float(grad_scale), _ptr(loss), _ptr(upstream),
-                             _ptr(g_final), int(bool(accumulate)), _ptr(plan_ws), _ptr(ws), _stream()),
-          "idg_na_nce_f32")
-    return loss
-
-
-def reg_rows_raw(ego, users, pos, neg, num_users, reg_lambda, g_ego=None, g_final=None, loss=None, plan_ws=None, ws=None):
-    """idg_reg_rows_f32: loss[1] = reg_lambda * 1/2 (sum |e_u|^2 + sum |e_p|^2 + sum |e_n|^2) / B over the ego rows of the
-    batch (duplicates counted); its gradient rows STORED to g_ego and zeros STORED to the same rows of g_final (both
-    optional).  plan_ws: a BPR workspace holding bpr_plan_raw(users, pos, neg, ...) of this batch; None: in-call."""
-    _require_device(ego, users, pos, neg, g_ego, g_final, loss)
-    _require_ids(users, pos, neg)
-    n, d = ego.shape
-    B = users.shape[0]
-    if pos.shape[0] != B or neg.shape[0] != B:
-        raise ValueError("reg_rows_raw: id lists of different lengths")
-    if ws is None:
-        ws = _na_ws(B, d, ego.device)
-    if loss is None:
-        loss = torch.empty(1, dtype=torch.float32, device=ego.device)
-    check(lib.idg_reg_rows_f32(_ptr(ego), n, d, _ptr(users), _ptr(pos), _ptr(neg), B, int(num_users), float(reg_lambda),
-                               _ptr(loss), _ptr(g_ego), _ptr(g_final), _ptr(plan_ws), _ptr(ws), _stream()),
-          "idg_reg_rows_f32")
-    return loss
-
-
-class _RegRows(torch.autograd.Function):
-    """The forward computes the loss only; the backward stores the gradient rows into a zeroed panel and scales them."""
-
-    @staticmethod
-    def forward(ctx, ego, users, pos, neg, num_users, reg_lambda):
-        _require_device(ego, users, pos, neg)
-        e = _f32c(ego.detach(), "ego")
-        users, pos, neg = _i64c(users, "users"), _i64c(pos, "pos"), _i64c(neg, "neg")
-        loss = reg_rows_raw(e, users, pos, neg, num_users, reg_lambda)
-        ctx.save_for_backward(e, users, pos, neg)
-        ctx.meta = (int(num_users), float(reg_lambda))
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        e, users, pos, neg = ctx.saved_tensors
-        num_users, reg_lambda = ctx.meta
-        g_ego = torch.zeros_like(e)
-        reg_rows_raw(e, users, pos, neg, num_users, reg_lambda, g_ego=g_ego)
-        return g_ego.mul_(g.to(torch.float32)), None, None, None, None, None
-
-
-def reg_rows_loss(ego, user, positive, negative, num_users, reg_lambda):
-    """reg_lambda * get_reg_loss(ego[user], ego[num_users + positive], ego[num_users + negative]) as a 0-d tensor,
-    differentiable w.r.t. the ego panel (LightCSCF on LightGCN: the regulariser without a BPR term)."""
-    return _RegRows.apply(ego, user, positive, negative, num_users, reg_lambda)
-
-
-class _NaNceLoss(torch.autograd.Function):
-    """The forward computes the loss only; the backward runs the call again with the incoming scalar as upstream."""
-
-    @staticmethod
-    def forward(ctx, final, users, pos, num_users, temperature, margin, weight):
-        _require_device(final, users, pos)
-        fin = _f32c(final.detach(), "final")
-        users, pos = _i64c(users, "users"), _i64c(pos, "pos")
-        loss = na_nce_loss_raw(fin, users, pos, num_users, temperature, margin, weight)
-        ctx.save_for_backward(fin, users, pos)
-        ctx.meta = (int(num_users), float(temperature), margin, float(weight))
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        fin, users, pos = ctx.saved_tensors
-        num_users, temperature, margin, weight = ctx.meta
-        up = g.to(torch.float32).reshape(1).contiguous()
-        g_final = torch.zeros_like(fin)
-        na_nce_loss_raw(fin, users, pos, num_users, temperature, margin, weight, g_final, upstream=up, accumulate=True)
-        return g_final, None, None, None, None, None, None
-
-
-def na_nce_loss(final, user, positive, num_users, temperature, margin=None, weight=1.0):
-    """weight * the neighbour-aggregation loss of LightCCF (margin None) / LightCSCF (margin = lambda_margin) as a 0-d tensor,
-    differentiable w.r.t. the [num_users + num_items, d] panel."""
-    return _NaNceLoss.apply(final, user, positive, num_users, temperature, margin, weight)
-
-
-# ----------------------------------------------------------------------------------- CVGA (idg_vae.hip)
-def multinomial_nll_workspace(B, I, d, device):
-    """A private idg_multinomial_nll_f32 buffer: O(chunks B d + B), never B x I.  It also keeps the row statistics of the
-    last forward call made with it."""
-    return torch.empty(int(lib.idg_multinomial_nll_workspace_bytes(int(B), int(I), int(d))), dtype=torch.uint8, device=device)
-
-
-def multinomial_nll_raw(Z, W, c, users, indptr, items, values, loss=None, upstream=None, gZ=None, gW=None, gc=None,
-                        stats_ready=False, ws=None):
-    """idg_multinomial_nll_f32: loss[1] = (1/B) sum_b (n_b LSE_b - sum_i x_bi l_bi), l = Z W^T + c, x_b = row users[b] of
-    the device train CSR (indptr, items, values) — get_ELBO_loss's BCE term on decode(z) (models/CVGA.py:55-75).
-    gZ / gW / gc (all or none, stored): its gradients scaled by `upstream` (device [1]; None = 1).  stats_ready: the row
-    statistics in `ws` from a forward call on the same inputs are reused.  Returns (loss, ws)."""
-    _require_device(Z, W, c, users, indptr, items, values, loss, upstream, gZ, gW, gc, ws)
-    _require_ids(users)
-    B, d = Z.shape
-    I = W.shape[0]
-    for t, name in ((Z, "Z"), (W, "W"), (c, "c"), (values, "values")):
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise TypeError("multinomial_nll_raw: %s must be contiguous float32" % name)
-    if W.shape[1] != d or c.shape[0] != I or indptr.dtype != torch.int64 or items.dtype != torch.int32:
-        raise TypeError("multinomial_nll_raw: Z [B, d], W [I, d], c [I], indptr int64, items int32")
-    if ws is None:
-        ws = multinomial_nll_workspace(B, I, d, Z.device)
-    if loss is None and gZ is None:
-        loss = torch.empty(1, dtype=torch.float32, device=Z.device)
-    check(lib.idg_multinomial_nll_f32(_ptr(Z), _ptr(W), _ptr(c), B, I, d, _ptr(users), _ptr(indptr), _ptr(items), _ptr(values),
-                                      _ptr(loss), _ptr(upstream), _ptr(gZ), _ptr(gW), _ptr(gc),
-                                      native.IDG_NLL_STATS_READY if stats_ready else 0, _ptr(ws), _stream()),
-          "idg_multinomial_nll_f32")
-    return loss, ws
-
-
-class _MultinomialNLL(torch.autograd.Function):
-    """The forward keeps its workspace (the row max / sum-exp statistics); the backward runs only the gradient pass."""
-
-    @staticmethod
-    def forward(ctx, Z, W, c, users, indptr, items, values):
-        Z, W, c = _f32c(Z.detach(), "Z"), _f32c(W.detach(), "W"), _f32c(c.detach(), "c")
-        users = _i64c(users, "users")
-        loss, ws = multinomial_nll_raw(Z, W, c, users, indptr, items, values)
-        ctx.save_for_backward(Z, W, c, users, indptr, items, values)
-        ctx.ws = ws
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        Z, W, c, users, indptr, items, values = ctx.saved_tensors
-        up = g.to(torch.float32).reshape(1).contiguous()
-        gZ, gW, gc = torch.empty_like(Z), torch.empty_like(W), torch.empty_like(c)
-        multinomial_nll_raw(Z, W, c, users, indptr, items, values, upstream=up, gZ=gZ, gW=gW, gc=gc, stats_ready=True,
-                            ws=ctx.ws)
-        return gZ, gW, gc, None, None, None, None
-
-
-def multinomial_nll(Z, W, c, users, indptr, items, values):
-    """-mean_b sum_i log_softmax(Z W^T + c)_bi x_bi (losses.py:54) with x the users' rows of the device train CSR, as a
-    0-d tensor differentiable w.r.t. Z [B, d], W [I, d] and c [I]; the [B, I] logits are never stored."""
-    return _MultinomialNLL.apply(Z, W, c, users, indptr, items, values)
-
-
-# ----------------------------------------------------------------------------------- CGCL (idg_tnce.hip)
-TABLE_NCE_MAX_WIDTH = 256
-
-
-def _table_nce_args(table_panel, row0, N, query_panels, query_ids, pos_ids, weights, temperature):
-    """The checks of the full-table contrastive calls that need no device; returns (nq, B, d)."""
-    nq = len(query_panels)
-    if not 1 <= nq <= native.IDG_TNCE_MAX_QUERY_BLOCKS:
-        raise ValueError("table_nce: %d query blocks (1 .. %d share one table)" % (nq, native.IDG_TNCE_MAX_QUERY_BLOCKS))
-    if len(query_ids) != nq or len(weights) != nq:
-        raise ValueError("table_nce: %d query panels, %d id lists, %d weights" % (nq, len(query_ids), len(weights)))
-    if not float(temperature) > 0:
-        raise ValueError("table_nce: temperature must be positive (got %r)" % (temperature,))
-    if table_panel.dim() != 2:
-        raise ValueError("table_nce: the table panel must be [n, d]")
-    n, d = table_panel.shape
-    row0, N = int(row0), int(N)
-    if N < 1 or row0 < 0 or row0 + N > n:
-        raise ValueError("table_nce: rows [%d, %d) are not inside the [%d, %d] panel" % (row0, row0 + N, n, d))
-    if d > TABLE_NCE_MAX_WIDTH:
-        raise ValueError("table_nce: width %d (up to %d is built)" % (d, TABLE_NCE_MAX_WIDTH))
-    B = int(pos_ids.shape[0])
-    if B < 1:
-        raise ValueError("table_nce: empty batch")
-    for k in range(nq):
-        if query_panels[k].dim() != 2 or query_panels[k].shape[1] != d:
-            raise ValueError("table_nce: query panel %d is %s, the table is [*, %d]" % (k, tuple(query_panels[k].shape), d))
-        if query_ids[k].dim() != 1 or query_ids[k].shape[0] != B:
-            raise ValueError("table_nce: id list %d has %s entries, pos_ids %d" % (k, tuple(query_ids[k].shape), B))
-    return nq, B, int(d)
-
-
-def table_nce_workspace(B, N, d, nq, device):
-    """A private idg_table_nce_f32 buffer: the normalised copies, per-row statistics and ordered partial sums
-    (O((N + chunks nq B) d)), never B x N."""
-    nbytes = int(lib.idg_table_nce_workspace_bytes(int(B), int(N), int(d), int(nq)))
-    if nbytes == 0:
-        raise ValueError("table_nce_workspace: sizes that are not built (B=%d, N=%d, d=%d, nq=%d)" % (B, N, d, nq))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
-
-
-_tnce_ws_cache = {}
-
-
-def table_nce_raw(table_panel, row0, N, query_panels, query_ids, pos_ids, weights, temperature, loss=None, upstream=None,
-                  g_table=None, g_queries=None, ws=None):
-    """idg_table_nce_f32: loss[k] = -weights[k] sum_b log(exp(s_b,pos / tau) / sum_{j < N} exp(s_bj / tau) + 1e-7) with
-    s = normalize(query_panels[k][query_ids[k]]) . normalize(table_panel[row0 : row0 + N])^T and the positive of query b at
-    table row pos_ids[b] (models/CGCL.py:95-215's six terms; losses.get_InfoNCE_loss_all's expression).  g_table [n, d] and
-    g_queries (one panel per block; both or neither): the gradients of sum_k upstream[k] loss[k] (device [nq]; None = ones)
-    are ADDED into them — the caller zeroes, and may pass one tensor in several roles.  Returns the loss vector [nq]."""
-    nq, B, d = _table_nce_args(table_panel, row0, N, query_panels, query_ids, pos_ids, weights, temperature)
-    grads = g_table is not None or g_queries is not None
-    if grads and (g_table is None or g_queries is None or len(g_queries) != nq):
-        raise ValueError("table_nce_raw: g_table and one gradient panel per query block go together")
-    gq = list(g_queries) if grads else []
-    _require_device(table_panel, pos_ids, loss, upstream, g_table, ws, *query_panels, *query_ids, *gq)
-    _require_ids(pos_ids, *query_ids)
-    for t, ref in [(table_panel, None), (g_table, table_panel)] + [(q, None) for q in query_panels] + list(zip(gq, query_panels)):
-        if t is None:
-            continue
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise TypeError("table_nce_raw: panels must be contiguous float32")
-        if ref is not None and t.shape != ref.shape:
-            raise ValueError("table_nce_raw: a gradient panel of shape %s for a panel of shape %s" % (tuple(t.shape), tuple(ref.shape)))
-    dev = table_panel.device
-    if ws is None:
-        key = (B, int(N), d, nq, dev)
-        ws = _tnce_ws_cache.get(key)
-        if ws is None:
-            ws = _tnce_ws_cache[key] = table_nce_workspace(B, N, d, nq, dev)
-    if loss is None:
-        loss = torch.empty(nq, dtype=torch.float32, device=dev)
-    vp = C.c_void_p * nq
-    check(lib.idg_table_nce_f32(_ptr(table_panel), int(row0), int(N), d, nq, vp(*[_ptr(q) for q in query_panels]),
-                                vp(*[_ptr(i) for i in query_ids]), B, _ptr(pos_ids), (C.c_float * nq)(*[float(w) for w in weights]),
-                                float(temperature), _ptr(loss), _ptr(upstream), _ptr(g_table),
-                                vp(*[_ptr(g) for g in gq]) if grads else None, _ptr(ws), _stream()), "idg_table_nce_f32")
-    return loss
-
-
-class _TableNCE(torch.autograd.Function):
-    """The forward computes the losses only; the backward runs the call again with the incoming gradient scalars.  Distinct
-    tensors among (table, query panels) are the differentiable inputs; a tensor in several roles receives the sum."""
-
-    @staticmethod
-    def forward(ctx, meta, *panels):
-        roles, row0, N, ids, pos_ids, weights, temperature = meta
-        det = [_f32c(p.detach(), "panel") for p in panels]
-        table, queries = det[roles[0]], [det[r] for r in roles[1:]]
-        loss = table_nce_raw(table, row0, N, queries, ids, pos_ids, weights, temperature)
-        ctx.save_for_backward(*det)
-        ctx.meta = meta
-        return tuple(loss[k] for k in range(len(queries)))
-
-    @staticmethod
-    def backward(ctx, *gl):
-        det = ctx.saved_tensors
-        roles, row0, N, ids, pos_ids, weights, temperature = ctx.meta
-        up = torch.stack([g.to(torch.float32).reshape(()) for g in gl]).contiguous()
-        grads = [torch.zeros_like(p) for p in det]
-        table_nce_raw(det[roles[0]], row0, N, [det[r] for r in roles[1:]], ids, pos_ids, weights, temperature, upstream=up,
-                      g_table=grads[roles[0]], g_queries=[grads[r] for r in roles[1:]])
-        return (None,) + tuple(grads)
-
-
-def table_nce_loss(table_panel, row0, N, query_panels, query_ids, pos_ids, weights, temperature):
-    """The full-table contrastive terms as nq 0-d tensors, differentiable w.r.t. the table panel and every query panel (see
-    table_nce_raw).  The same tensor may be the table panel and a query panel, or serve several blocks: it is one
-    differentiable input and its gradients add."""
-    _table_nce_args(table_panel, row0, N, query_panels, query_ids, pos_ids, weights, temperature)
-    _require_device(table_panel, pos_ids, *query_panels, *query_ids)
-    panels, roles = [], []
-    for t in [table_panel] + list(query_panels):
-        for i, p in enumerate(panels):
-            if p is t:
-                roles.append(i)
-                break
-        else:
-            roles.append(len(panels))
-            panels.append(t)
-    ids = [_i64c(i, "query_ids") for i in query_ids]
-    meta = (tuple(roles), int(row0), int(N), ids, _i64c(pos_ids, "pos_ids"), [float(w) for w in weights], float(temperature))
-    return _TableNCE.apply(meta, *panels)
-
-
-# ----------------------------------------------------------------------------------- MixRec's in-batch mixing terms
-MIX_NCE_MAX_WIDTH = 256
-_mix_ws_cache = {}
-
-
-def mix_nce_workspace(B, d, device):
-    """A private idg_mix_nce_f32 buffer (the normalised copies, per-row statistics and ordered partial sums: O(chunks B d))."""
-    nbytes = int(lib.idg_mix_nce_workspace_bytes(int(B), int(d)))
-    if nbytes == 0:
-        raise ValueError("mix_nce_workspace: sizes that are not built (B=%d, d=%d; d <= %d)" % (B, d, MIX_NCE_MAX_WIDTH))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
-
-
-def mix_nce_raw(panel, num_users, users, pos, neg, user_perm, item_perm, nu, user_beta, item_beta, temperature, ssl_weight,
-                loss=None, upstream=None, g_panel=None, ws=None):
-    """idg_mix_nce_f32 (include/idgrec.h states the math): loss[0] = (1 - item_beta) x the rectangular term of the users' rows
-    against the mixed negatives, loss[1] = ssl_weight x (the users' side + the positives' side), on rows of `panel` [n, d]
-    (users first).  user_perm / item_perm: int64 [B] permutations, nu: float32 [B], all on the device.  g_panel (None: losses
-    only): the gradient of upstream[0] loss[0] + upstream[1] loss[1] (device [2]; None = ones) w.r.t. the panel is ADDED
-    into the batch's rows.  Returns the loss pair."""
-    _require_device(panel, users, pos, neg, user_perm, item_perm, nu, loss, upstream, g_panel, ws)
-    _require_ids(users, pos, neg, user_perm, item_perm)
-    if panel.dim() != 2 or panel.dtype != torch.float32 or not panel.is_contiguous():
-        raise TypeError("mix_nce_raw: panel must be a contiguous float32 [n, d] tensor")
-    n, d = panel.shape
-    B = int(users.shape[0])
-    if B < 1 or any(tuple(t.shape) != (B,) for t in (users, pos, neg, user_perm, item_perm, nu)):
-        raise ValueError("mix_nce_raw: users, pos, neg, both permutations and nu are [B] with B >= 1")
-    if nu.dtype != torch.float32 or not nu.is_contiguous():
-        raise TypeError("mix_nce_raw: nu must be contiguous float32")
-    if g_panel is not None and (g_panel.dtype != torch.float32 or not g_panel.is_contiguous() or g_panel.shape != panel.shape):
-        raise ValueError("mix_nce_raw: g_panel must be a contiguous float32 tensor of the panel's shape")
-    if not 0 < int(num_users) < n:
-        raise ValueError("mix_nce_raw: num_users = %d of %d panel rows" % (int(num_users), n))
-    if ws is None:
-        key = (B, int(d), panel.device)
-        ws = _mix_ws_cache.get(key)
-        if ws is None:
-            ws = _mix_ws_cache[key] = mix_nce_workspace(B, d, panel.device)
-    if loss is None:
-        loss = torch.empty(2, dtype=torch.float32, device=panel.device)
-    check(lib.idg_mix_nce_f32(_ptr(panel), n, d, int(num_users), _ptr(users), _ptr(pos), _ptr(neg), B, _ptr(user_perm),
-                              _ptr(item_perm), _ptr(nu), float(user_beta), float(item_beta), float(temperature), float(ssl_weight),
-                              _ptr(loss), _ptr(upstream), _ptr(g_panel), _ptr(ws), _stream()), "idg_mix_nce_f32")
-    return loss
-
-
-class _MixNCE(torch.autograd.Function):
-    """The forward computes the two losses only; the backward runs the call again with the incoming gradient scalars."""
-
-    @staticmethod
-    def forward(ctx, panel, meta):
-        det = _f32c(panel.detach(), "panel")
-        loss = mix_nce_raw(det, *meta)
-        ctx.save_for_backward(det)
-        ctx.meta = meta
-        return loss[0], loss[1]
-
-    @staticmethod
-    def backward(ctx, g0, g1):
-        (det,) = ctx.saved_tensors
-        up = torch.stack([g0.to(torch.float32).reshape(()), g1.to(torch.float32).reshape(())]).contiguous()
-        g = torch.zeros_like(det)
-        mix_nce_raw(det, *ctx.meta, upstream=up, g_panel=g)
-        return g, None
-
-
-def mix_nce(panel, num_users, users, pos, neg, user_perm, item_perm, nu, user_beta, item_beta, temperature, ssl_weight):
-    """MixRec's two contrastive loss entries as 0-d tensors, differentiable w.r.t. the panel (see mix_nce_raw)."""
-    _require_device(panel, users, pos, neg, user_perm, item_perm, nu)
-    meta = (int(num_users), _i64c(users, "users"), _i64c(pos, "pos"), _i64c(neg, "neg"), _i64c(user_perm, "user_perm"),
-            _i64c(item_perm, "item_perm"), _f32c(nu, "nu"), float(user_beta), float(item_beta), float(temperature),
-            float(ssl_weight))
-    return _MixNCE.apply(panel, meta)
-
-
-# ----------------------------------------------------------------------------------- LightGCL (idg_svdnce.hip)
-LOWRANK_MAX_RANK = 16
-SVD_NCE_MAX_WIDTH = 256
-_lowrank_ws_cache = {}
-_svd_nce_ws_cache = {}
-
-
-def _rows_panel(who, t, name):
-    """A float32 [rows, w] device tensor read where it lies: unit column stride, any row stride >= w."""
-    if t.dim() != 2 or t.dtype != torch.float32:
-        raise TypeError("%s: %s must be a float32 [rows, width] tensor" % (who, name))
-    if t.shape[1] > 1 and t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    return t
-
-
-def _lowrank_sizes(who, A, d, n):
-    q = int(A.shape[1])
-    if not 1 <= q <= LOWRANK_MAX_RANK:
-        raise ValueError("%s: rank %d (1 .. %d are built)" % (who, q, LOWRANK_MAX_RANK))
-    if not 1 <= d <= SVD_NCE_MAX_WIDTH:
-        raise ValueError("%s: width %d (1 .. %d are built)" % (who, d, SVD_NCE_MAX_WIDTH))
-    if n < 1:
-        raise ValueError("%s: no rows" % who)
-    return q
-
-
-def _lowrank_rows(who, A, a_rows, n_default):
-    if a_rows is None:
-        return int(n_default)
-    _require_ids(a_rows)
-    if a_rows.dim() != 1:
-        raise ValueError("%s: a_rows must be a 1-d id list" % who)
-    return int(a_rows.shape[0])
-
-
-def lowrank_project_raw(A, X, out=None, a_rows=None, accumulate=False, ws=None):
-    """idg_lowrank_project_f32: out [q, d] (+)= sum_r A[a_rows[r] if a_rows is given else r]^T X[r], a tall deterministic
-    reduction.  A [*, q] and X [n, d] are read with their own row strides; a_rows: int64 [n] rows of A (may repeat)."""
-    _require_device(A, X, out, a_rows, ws)
-    A, X = _rows_panel("lowrank_project_raw", A, "A"), _rows_panel("lowrank_project_raw", X, "X")
-    n, d = int(X.shape[0]), int(X.shape[1])
-    q = _lowrank_sizes("lowrank_project_raw", A, d, n)
-    if _lowrank_rows("lowrank_project_raw", A, a_rows, A.shape[0]) != n:
-        raise ValueError("lowrank_project_raw: %d rows of A for %d rows of X" % (A.shape[0] if a_rows is None else a_rows.shape[0], n))
-    if out is None:
-        if accumulate:
-            raise ValueError("lowrank_project_raw: accumulate needs `out`")
-        out = torch.empty((q, d), dtype=torch.float32, device=X.device)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (q, d):
-        raise ValueError("lowrank_project_raw: out must be a contiguous float32 [%d, %d] tensor" % (q, d))
-    if ws is None:
-        key = (n, q, d, X.device)
-        ws = _lowrank_ws_cache.get(key)
-        if ws is None:
-            ws = _lowrank_ws_cache[key] = torch.empty(int(lib.idg_lowrank_project_workspace_bytes(n, q, d)), dtype=torch.uint8,
-                                                      device=X.device)
-    check(lib.idg_lowrank_project_f32(_ptr(A), _ld(A), _ptr(a_rows), _ptr(X), _ld(X), n, q, d, _ptr(out), int(bool(accumulate)),
-                                      _ptr(ws), _stream()), "idg_lowrank_project_f32")
-    return out
-
-
-def lowrank_expand_raw(A, P, Y=None, a_rows=None, scale=1.0, accumulate=False):
-    """idg_lowrank_expand_f32: Y[r] (+)= scale A[a_rows[r] if a_rows is given else r] P for every row r of Y.  A [*, q],
-    P [q, d]; Y [n, d] is written with its own row stride."""
-    _require_device(A, P, Y, a_rows)
-    A = _rows_panel("lowrank_expand_raw", A, "A")
-    P = _f32c(P, "P")
-    if P.dim() != 2 or P.shape[0] != A.shape[1]:
-        raise ValueError("lowrank_expand_raw: P is %s, A is [*, %d]" % (tuple(P.shape), A.shape[1]))
-    d = int(P.shape[1])
-    n = _lowrank_rows("lowrank_expand_raw", A, a_rows, A.shape[0])
-    q = _lowrank_sizes("lowrank_expand_raw", A, d, n)
-    if Y is None:
-        if accumulate:
-            raise ValueError("lowrank_expand_raw: accumulate needs `Y`")
-        Y = torch.empty((n, d), dtype=torch.float32, device=P.device)
-    elif (Y.dim() != 2 or Y.dtype != torch.float32 or tuple(Y.shape) != (n, d) or (d > 1 and Y.stride(1) != 1)
-          or (n > 1 and Y.stride(0) < d)):
-        raise ValueError("lowrank_expand_raw: Y must be a float32 [%d, %d] tensor with unit column stride" % (n, d))
-    check(lib.idg_lowrank_expand_f32(_ptr(A), _ld(A), _ptr(a_rows), _ptr(P), n, q, d, float(scale), int(bool(accumulate)),
-                                     _ptr(Y), _ld(Y), _stream()), "idg_lowrank_expand_f32")
-    return Y
-
-
-class _LowrankProject(torch.autograd.Function):
-    """out = A[rows]^T X, differentiable w.r.t. X (the factors are constants): gX = A[rows] g_out."""
-
-    @staticmethod
-    def forward(ctx, X, A, a_rows):
-        ctx.A, ctx.a_rows = A, a_rows
-        return lowrank_project_raw(A, X.detach(), a_rows=a_rows)
-
-    @staticmethod
-    def backward(ctx, g):
-        return lowrank_expand_raw(ctx.A, _f32c(g, "grad"), a_rows=ctx.a_rows), None, None
-
-
-class _LowrankExpand(torch.autograd.Function):
-    """Y = scale A[rows] P, differentiable w.r.t. P: gP = scale A[rows]^T gY."""
-
-    @staticmethod
-    def forward(ctx, P, A, a_rows, scale):
-        ctx.A, ctx.a_rows, ctx.scale = A, a_rows, scale
-        return lowrank_expand_raw(A, P.detach(), a_rows=a_rows, scale=scale)
-
-    @staticmethod
-    def backward(ctx, g):
-        gP = lowrank_project_raw(ctx.A, g, a_rows=ctx.a_rows)
-        return (gP if ctx.scale == 1.0 else gP * ctx.scale), None, None, None
-
-
-def lowrank_project(A, X, a_rows=None):
-    """A[a_rows]^T X as a [q, d] tensor, differentiable w.r.t. X (see lowrank_project_raw)."""
-    _require_device(A, X, a_rows)
-    return _LowrankProject.apply(X, A.detach(), None if a_rows is None else _i64c(a_rows, "a_rows"))
-
-
-def lowrank_expand(A, P, a_rows=None, scale=1.0):
-    """scale A[a_rows] P as an [n, d] tensor, differentiable w.r.t. P (see lowrank_expand_raw)."""
-    _require_device(A, P, a_rows)
-    return _LowrankExpand.apply(P, A.detach(), None if a_rows is None else _i64c(a_rows, "a_rows"), float(scale))
-
-
-def _svd_nce_args(final_panel, ego_panel, row0, N, AS, P, ids, temperature):
-    """The checks of the SVD-view contrastive calls that need no device; returns (B, d, q)."""
-    if not float(temperature) > 0:
-        raise ValueError("svd_nce: temperature must be positive (got %r)" % (temperature,))
-    if final_panel.dim() != 2 or ego_panel.shape != final_panel.shape:
-        raise ValueError("svd_nce: the final and ego panels must both be [n, d]")
-    n, d = final_panel.shape
-    row0, N = int(row0), int(N)
-    if N < 1 or row0 < 0 or row0 + N > n:
-        raise ValueError("svd_nce: rows [%d, %d) are not inside the [%d, %d] panel" % (row0, row0 + N, n, d))
-    if d > SVD_NCE_MAX_WIDTH:
-        raise ValueError("svd_nce: width %d (up to %d is built)" % (d, SVD_NCE_MAX_WIDTH))
-    if AS.dim() != 2 or AS.shape[0] != N or not 1 <= AS.shape[1] <= LOWRANK_MAX_RANK:
-        raise ValueError("svd_nce: the factor rows are %s, the side has %d rows (rank 1 .. %d)" % (tuple(AS.shape), N, LOWRANK_MAX_RANK))
-    q = int(AS.shape[1])
-    if tuple(P.shape) != (q, d):
-        raise ValueError("svd_nce: P is %s, expected [%d, %d]" % (tuple(P.shape), q, d))
-    if ids.dim() != 1 or ids.shape[0] < 1:
-        raise ValueError("svd_nce: empty batch")
-    return int(ids.shape[0]), int(d), q
-
-
-def svd_nce_workspace(B, N, d, q, device):
-    """A private idg_svd_nce_f32 buffer: the padded copies, per-chunk statistics and ordered partial sums
-    (O((N + chunks B) d)), never B x N."""
-    nbytes = int(lib.idg_svd_nce_workspace_bytes(int(B), int(N), int(d), int(q)))
-    if nbytes == 0:
-        raise ValueError("svd_nce_workspace: sizes that are not built (B=%d, N=%d, d=%d, q=%d)" % (B, N, d, q))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
-
-
-def svd_nce_raw(final_panel, ego_panel, row0, N, AS, P, ids, temperature, loss=None, upstream=None, g_final=None, g_ego=None,
-                dP=None, ws=None):
-    """idg_svd_nce_f32 (include/idgrec.h states the math), one side: with g_b = ego_panel[row0 + ids[b]] + AS[ids[b]] P and
-    s_bj = <g_b, final_panel[row0 + j]> / temperature, loss[0] = mean_b log(sum_{j < N} exp(s_bj) + 1e-8) and
-    loss[1] = mean_b clamp(<final_panel[row0 + ids[b]], g_b> / temperature, -5, 5).  g_final, g_ego [n, d] and dP [q, d] (all
-    or none): the gradient of upstream[0] loss[0] + upstream[1] loss[1] (device [2]; None = ones) is ADDED into the two panels
-    — the caller zeroes — and dP is stored.  Returns the loss pair."""
-    B, d, q = _svd_nce_args(final_panel, ego_panel, row0, N, AS, P, ids, temperature)
-    outs = (g_final, g_ego, dP)
-    grads = any(t is not None for t in outs)
-    if grads and any(t is None for t in outs):
-        raise ValueError("svd_nce_raw: g_final, g_ego and dP go together")
-    _require_device(final_panel, ego_panel, AS, P, ids, loss, upstream, g_final, g_ego, dP, ws)
-    _require_ids(ids)
-    for t, shape in ((final_panel, None), (ego_panel, None), (AS, None), (P, None), (g_final, final_panel.shape),
-                     (g_ego, final_panel.shape), (dP, (q, d))):
-        if t is None:
-            continue
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise TypeError("svd_nce_raw: panels, factors and P must be contiguous float32")
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise ValueError("svd_nce_raw: a gradient output of shape %s, expected %s" % (tuple(t.shape), tuple(shape)))
-    dev = final_panel.device
-    if ws is None:
-        key = (B, int(N), d, q, dev)
-        ws = _svd_nce_ws_cache.get(key)
-        if ws is None:
-            ws = _svd_nce_ws_cache[key] = svd_nce_workspace(B, N, d, q, dev)
-    if loss is None:
-        loss = torch.empty(2, dtype=torch.float32, device=dev)
-    check(lib.idg_svd_nce_f32(_ptr(final_panel), _ptr(ego_panel), int(row0), int(N), d, _ptr(AS), q, _ptr(P), _ptr(ids), B,
-                              float(temperature), _ptr(loss), _ptr(upstream), _ptr(g_final), _ptr(g_ego), _ptr(dP), _ptr(ws),
-                              _stream()), "idg_svd_nce_f32")
-    return loss
-
-
-class _SvdNCE(torch.autograd.Function):
-    """The forward computes the two losses only; the backward runs the call again with the incoming gradient scalars."""
-
-    @staticmethod
-    def forward(ctx, final_panel, ego_panel, P, meta):
-        det = [_f32c(t.detach(), "panel") for t in (final_panel, ego_panel, P)]
-        row0, N, AS, ids, temperature = meta
-        loss = svd_nce_raw(det[0], det[1], row0, N, AS, det[2], ids, temperature)
-        ctx.save_for_backward(*det)
-        ctx.meta = meta
-        return loss[0], loss[1]
-
-    @staticmethod
-    def backward(ctx, g0, g1):
-        F, E, P = ctx.saved_tensors
-        row0, N, AS, ids, temperature = ctx.meta
-        up = torch.stack([g0.to(torch.float32).reshape(()), g1.to(torch.float32).reshape(())]).contiguous()
-        gF, gE, dP = torch.zeros_like(F), torch.zeros_like(E), torch.empty_like(P)
-        svd_nce_raw(F, E, row0, N, AS, P, ids, temperature, upstream=up, g_final=gF, g_ego=gE, dP=dP)
-        return gF, gE, dP, None
-
-
-def svd_nce_loss(final_panel, ego_panel, row0, N, AS, P, ids, temperature):
-    """LightGCL's two contrastive terms of one side — (log-sum-exp term, clamped positive term) — as 0-d tensors,
-    differentiable w.r.t. the final panel, the ego panel and P (see svd_nce_raw); AS, the side's factor rows times the
-    singular values, is a constant."""
-    _svd_nce_args(final_panel, ego_panel, row0, N, AS, P, ids, temperature)
-    _require_device(final_panel, ego_panel, AS, P, ids)
-    meta = (int(row0), int(N), _f32c(AS.detach(), "AS"), _i64c(ids, "ids"), float(temperature))
-    return _SvdNCE.apply(final_panel, ego_panel, P, meta)
-
-
-# ----------------------------------------------------------------------------------- k-means (NCL's E-step)
-KMEANS_MAX_WIDTH = 256
-_kmeans_ws_cache = {}
-
-
-def kmeans_workspace(N, K, d, device):
-    """A private idg_kmeans_* buffer: the padded copies of X and C, the per-chunk minima and the sorted row ids
-    (O((N + K) d + chunks N)), never N x K."""
-    nbytes = int(lib.idg_kmeans_workspace_bytes(int(N), int(K), int(d)))
-    if nbytes == 0:
-        raise ValueError("kmeans_workspace: sizes that are not built (N=%d, K=%d, d=%d)" % (N, K, d))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
-
-
-def _kmeans_args(who, X, K, C=None, assign=None, ws=None, **outs):
-    """The checks of the k-means calls; returns (N, d, ldx, ws).  X: [N, d] float32 with unit column stride (a row stride above
-    d — a column slice of a wider panel — is passed through as ldx)."""
-    if X.dim() != 2:
-        raise ValueError("%s: X must be [N, d]" % who)
-    N, d = (int(v) for v in X.shape)
-    K = int(K)
-    if N < 1 or K < 1:
-        raise ValueError("%s: bad sizes (N = %d, K = %d)" % (who, N, K))
-    if d < 1 or d > KMEANS_MAX_WIDTH:
-        raise ValueError("%s: width %d (1 .. %d is built)" % (who, d, KMEANS_MAX_WIDTH))
-    if X.dtype != torch.float32 or X.stride(1) != 1 or (N > 1 and X.stride(0) < d):
-        raise TypeError("%s: X must be float32 with contiguous rows (got %s, strides %s)" % (who, X.dtype, tuple(X.stride())))
-    if C is not None and (C.dtype != torch.float32 or not C.is_contiguous() or tuple(C.shape) != (K, d)):
-        raise TypeError("%s: the centroids must be a contiguous float32 [%d, %d] tensor" % (who, K, d))
-    if assign is not None and (assign.dtype != torch.int32 or not assign.is_contiguous() or tuple(assign.shape) != (N,)):
-        raise TypeError("%s: assign must be a contiguous int32 [%d] tensor" % (who, N))
-    for name, (t, dtype, shape) in outs.items():
-        if t is not None and (t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape):
-            raise TypeError("%s: %s must be a contiguous %s tensor of shape %s" % (who, name, dtype, shape))
-    _require_device(X, C, assign, ws, *[t for t, _, _ in outs.values()])
-    if ws is None:
-        key = (N, K, d, X.device)
-        ws = _kmeans_ws_cache.get(key)
-        if ws is None:
-            ws = _kmeans_ws_cache[key] = kmeans_workspace(N, K, d, X.device)
-    return N, d, (int(X.stride(0)) if N > 1 else d), ws
-
-
-def kmeans_assign_raw(X, C, assign=None, dist2=None, ws=None):
-    """idg_kmeans_assign_f32: assign[i] = argmin_j ||X[i] - C[j]||^2 (int32, ties to the lowest j) and, when `dist2` is given,
-    that squared distance.  Returns assign."""
-    K = C.shape[0] if C.dim() == 2 else 0
-    if assign is None and X.dim() == 2:
-        assign = torch.empty(X.shape[0], dtype=torch.int32, device=X.device)
-    N, d, ldx, ws = _kmeans_args("kmeans_assign_raw", X, K, C, assign, ws,
-                                 dist2=(dist2, torch.float32, (int(X.shape[0]),) if X.dim() == 2 else ()))
-    check(lib.idg_kmeans_assign_f32(_ptr(X), ldx, N, d, _ptr(C), int(K), _ptr(assign), _ptr(dist2), _ptr(ws), _stream()),
-          "idg_kmeans_assign_f32")
-    return assign
-
-
-def kmeans_update_raw(X, assign, C, counts=None, ws=None):
-    """idg_kmeans_update_f32: C[j] <- the mean of the rows of X with assign[i] = j, in place (a cluster without rows keeps its
-    centroid); counts (optional int32 [K]) <- the rows per cluster.  Returns C."""
-    K = C.shape[0] if C.dim() == 2 else 0
-    N, d, ldx, ws = _kmeans_args("kmeans_update_raw", X, K, C, assign, ws, counts=(counts, torch.int32, (int(K),)))
-    check(lib.idg_kmeans_update_f32(_ptr(X), ldx, N, d, _ptr(assign), int(K), _ptr(C), _ptr(counts), _ptr(ws), _stream()),
-          "idg_kmeans_update_f32")
-    return C
-
-
-def kmeans_raw(X, C, niter, assign=None, inertia=None, ws=None):
-    """idg_kmeans_f32: niter x (assign, update) from the centroids in C (updated in place), then the assignment against the
-    final centroids; inertia (optional float32 [niter + 1]) <- the sum of squared distances of every assignment.  One chain
-    of launches, nothing read back.  Returns (C, assign)."""
-    niter = int(niter)
-    if niter < 0:
-        raise ValueError("kmeans_raw: niter = %d" % niter)
-    K = C.shape[0] if C.dim() == 2 else 0
-    if assign is None and X.dim() == 2:
-        assign = torch.empty(X.shape[0], dtype=torch.int32, device=X.device)
-    N, d, ldx, ws = _kmeans_args("kmeans_raw", X, K, C, assign, ws, inertia=(inertia, torch.float32, (niter + 1,)))
-    check(lib.idg_kmeans_f32(_ptr(X), ldx, N, d, int(K), niter, _ptr(C), _ptr(assign), _ptr(inertia), _ptr(ws), _stream()),
-          "idg_kmeans_f32")
-    return C, assign
-
-
-def kmeans(X, K, niter=25, seed=1234):
-    """Lloyd's k-means of the rows of X [N, d] on the device (what models/NCL.py:66-74 asks of faiss.Kmeans + index.search):
-    (centroids [K, d], assign int32 [N], inertia [niter + 1]).  The initial centroids are the rows
-    torch.randperm(N, generator=<CPU generator seeded with `seed`>)[:K] of X: distinct rows, the same row indices for the same
-    N and seed.  A cluster that loses all its rows keeps its centroid."""
-    if X.dim() != 2:
-        raise ValueError("kmeans: X must be [N, d]")
-    N, K = int(X.shape[0]), int(K)
-    if K < 1 or K > N:
-        raise ValueError("kmeans: K = %d clusters for N = %d rows" % (K, N))
-    if X.dtype != torch.float32:
-        raise TypeError("kmeans: X must be float32 (got %s)" % X.dtype)
-    _require_device(X)
-    first = torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))[:K].to(X.device)
-    C = X.detach().index_select(0, first).contiguous()
-    inertia = torch.empty(int(niter) + 1, dtype=torch.float32, device=X.device)
-    C, assign = kmeans_raw(X.detach(), C, niter, inertia=inertia)
-    return C, assign, inertia
-
-
-_head_ws = {}
-
-
-def _head_workspace(B, device):
-    key = (int(B), device)
-    ws = _head_ws.get(key)
-    if ws is None:
-        ws = _head_ws[key] = torch.empty(int(lib.idg_vae_head_workspace_bytes(int(B))), dtype=torch.uint8, device=device)
-    return ws
-
-
-def _head_args(name, pre, users, bias, pre_rows, **rows_d):
-    """Shapes of the head's operands: pre [*, 2d] (row b read at pre_rows[b], else b), bias [2d], users / pre_rows
-    contiguous int64 [B]; every tensor in rows_d contiguous float32 with B rows of the stated width.  Returns (B, d)."""
-    _require_ids(users)
-    B = int(users.shape[0])
-    if pre.dtype != torch.float32 or not pre.is_contiguous() or pre.dim() != 2 or pre.shape[1] % 2:
-        raise TypeError("%s: pre must be a contiguous float32 [*, 2d] tensor" % name)
-    d = int(pre.shape[1]) // 2
-    if bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != 2 * d:
-        raise TypeError("%s: bias must be a contiguous float32 [2d] tensor" % name)
-    if pre_rows is None:
-        if pre.shape[0] < B:
-            raise ValueError("%s: pre has fewer than B rows" % name)
-    else:
-        _require_ids(pre_rows)
-        if pre_rows.shape[0] != B:
-            raise ValueError("%s: pre_rows must hold B ids" % name)
-    for key, (t, width) in rows_d.items():
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, width * d)):
-            raise TypeError("%s: %s must be a contiguous float32 [%d, %d] tensor" % (name, key, B, width * d))
-    return B, d
-
-
-def vae_head_raw(pre, users, bias, p, seed, stream_id, z=None, kl=None, eps=None, pre_rows=None, eps_out=None, keep_out=None,
-                 with_kl=True):
-    """idg_vae_head_fwd_f32: z [B, d] = eps * exp(logvar / 2) + mu with (mu | logvar) = dropout_p(pre[row] + bias) and
-    kl [1] = -0.5 / B^2 sum (1 + logvar - mu^2 - exp logvar) (models/CVGA.py:40-67, losses.py:55).  pre: [B, 2d], or a
-    [*, 2d] panel read at pre_rows[b].  eps: [B, d] injected noise; None: drawn from (seed, stream_id, user, feature).
-    with_kl=False: z only (kl is NULL for the library and None here).  Returns (z, kl)."""
-    _require_device(pre, users, bias, z, kl, eps, pre_rows, eps_out, keep_out)
-    B, d = _head_args("vae_head_raw", pre, users, bias, pre_rows, z=(z, 1), eps=(eps, 1), eps_out=(eps_out, 1),
-                      keep_out=(keep_out, 2))
-    if kl is not None and (kl.dtype != torch.float32 or kl.numel() < 1):
-        raise TypeError("vae_head_raw: kl must be a float32 tensor of at least one element")
-    if z is None:
-        z = torch.empty((B, d), dtype=torch.float32, device=pre.device)
-    if not with_kl:
-        kl = None
-    elif kl is None:
-        kl = torch.empty(1, dtype=torch.float32, device=pre.device)
-    check(lib.idg_vae_head_fwd_f32(_ptr(pre), 2 * d, _ptr(pre_rows), _ptr(users), B, d, _ptr(bias), float(p), C.c_uint64(seed),
-                                   C.c_uint64(stream_id), _ptr(eps), _ptr(z), _ptr(kl), _ptr(eps_out), _ptr(keep_out),
-                                   _ptr(_head_workspace(B, pre.device)), _stream()), "idg_vae_head_fwd_f32")
-    return z, kl
-
-
-def vae_head_bwd_raw(pre, users, bias, p, seed, stream_id, gz, gpre, upstream_kl=None, gbias=None, eps=None, pre_rows=None,
-                     gpre_rows=None):
-    """idg_vae_head_bwd_f32: gpre rows (gpre_rows[b], distinct, or b) <- keep * d/d(mu | logvar) of the decoder loss (through
-    gz = d L / d z) plus upstream_kl * KL; gbias (optional) <- their column sums in batch order.  keep and eps are
-    regenerated from the forward's (seed, stream_id) — or eps is the same injected tensor."""
-    _require_device(pre, users, bias, gz, gpre, upstream_kl, gbias, eps, pre_rows, gpre_rows)
-    B, d = _head_args("vae_head_bwd_raw", pre, users, bias, pre_rows, gz=(gz, 1), eps=(eps, 1))
-    if gpre.dtype != torch.float32 or not gpre.is_contiguous() or gpre.dim() != 2 or gpre.shape[1] != 2 * d:
-        raise TypeError("vae_head_bwd_raw: gpre must be a contiguous float32 [*, 2d] tensor")
-    if gpre_rows is None:
-        if gpre.shape[0] < B:
-            raise ValueError("vae_head_bwd_raw: gpre has fewer than B rows")
-    else:
-        _require_ids(gpre_rows)
-        if gpre_rows.shape[0] != B:
-            raise ValueError("vae_head_bwd_raw: gpre_rows must hold B ids")
-    if gbias is not None and (gbias.dtype != torch.float32 or not gbias.is_contiguous() or gbias.numel() != 2 * d):
-        raise TypeError("vae_head_bwd_raw: gbias must be a contiguous float32 [2d] tensor")
-    if upstream_kl is not None and (upstream_kl.dtype != torch.float32 or upstream_kl.numel() < 1):
-        raise TypeError("vae_head_bwd_raw: upstream_kl must be a float32 tensor of at least one element")
-    check(lib.idg_vae_head_bwd_f32(_ptr(pre), 2 * d, _ptr(pre_rows), _ptr(users), B, d, _ptr(bias), float(p), C.c_uint64(seed),
-                                   C.c_uint64(stream_id), _ptr(eps), _ptr(gz), _ptr(upstream_kl), _ptr(gpre), 2 * d,
-                                   _ptr(gpre_rows), _ptr(gbias), _stream()), "idg_vae_head_bwd_f32")
-
-
-class _VaeHead(torch.autograd.Function):
-    """(z, kl) of the batch rows pre [B, 2d]; the backward regenerates the mask and eps from (seed, stream_id)."""
-
-    @staticmethod
-    def forward(ctx, pre, bias, users, p, seed, stream_id, eps):
-        pre, bias = _f32c(pre.detach(), "pre"), _f32c(bias.detach(), "bias")
-        users = _i64c(users, "users")
-        z, kl = vae_head_raw(pre, users, bias, p, seed, stream_id, eps=eps)
-        ctx.save_for_backward(pre, bias, users, eps)
-        ctx.meta = (float(p), int(seed), int(stream_id))
-        return z, kl[0]
-
-    @staticmethod
-    def backward(ctx, gz, gkl):
-        pre, bias, users, eps = ctx.saved_tensors
-        p, seed, sid = ctx.meta
-        gz = None if gz is None else _f32c(gz, "gz")
-        up = (torch.zeros(1, dtype=torch.float32, device=pre.device) if gkl is None
-              else gkl.to(torch.float32).reshape(1).contiguous())
-        gpre, gbias = torch.empty_like(pre), torch.empty_like(bias)
-        vae_head_bwd_raw(pre, users, bias, p, seed, sid, gz, gpre, upstream_kl=up, gbias=gbias, eps=eps)
-        return gpre, gbias, None, None, None, None, None
-
-
-def vae_head(pre, bias, users, p, stream=None, eps=None):
-    """CVGA's head on the batch's encoder rows pre [B, 2d] (models/CVGA.py:40-67): dropout p on (pre + bias), split into
-    mu / logvar, z = mu + eps * exp(logvar / 2), and the KL term.  Returns (z [B, d], kl 0-d), differentiable w.r.t. pre
-    and bias.  stream: (seed, stream id) of the mask and the noise (default: the next noise stream)."""
-    seed, sid = _next_noise_stream() if stream is None else stream
-    if eps is not None:
-        eps = _f32c(eps.detach(), "eps")
-    return _VaeHead.apply(pre, bias, users, p, seed, sid, eps)
 
 
 def spmm_rows_width(d):
@@ -3034,156 +1897,3 @@ class _EncodeRows(torch.autograd.Function):
 def encode_rows(graph, Wt, users):
     """(R_hat . Wt)[users] — the encoder layer of CVGA (models/CVGA.py:40-43, without its bias) at the batch's rows only."""
     return _EncodeRows.apply(Wt, graph, users)
-
-
-# ----------------------------------------------------------------------------------- Adam
-def adam_step_raw(param, grad, exp_avg, exp_avg_sq, lr, step, beta1=0.9, beta2=0.999, eps=1e-8):
-    _require_device(param, grad, exp_avg, exp_avg_sq)
-    for t in (param, grad, exp_avg, exp_avg_sq):
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise TypeError("adam_step_raw needs contiguous float32 tensors")
-    check(lib.idg_adam_step_f32(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), float(lr),
-                                float(beta1), float(beta2), float(eps), int(step), _stream()), "idg_adam_step_f32")
-
-
-class Adam(torch.optim.Optimizer):
-    """torch.optim.Adam's default algorithm (utility/utility_train/trainer.py:11) as one HIP
-    kernel per parameter tensor.  Same constructor signature for the arguments the reference
-    uses; weight decay / amsgrad are not part of the reference path and are rejected."""
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
-        if weight_decay != 0 or amsgrad:
-            raise NotImplementedError("idgrec_amd.Adam implements the reference's plain Adam only")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for group in self.param_groups:
-            b1, b2 = group["betas"]
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["step"] += 1
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                adam_step_raw(p.data, g, st["exp_avg"], st["exp_avg_sq"], group["lr"], st["step"], b1, b2, group["eps"])
-        return loss
-
-
-# --------------------------------------------------------------------------- scoring/top-K
-def score_dense(user_panel, item_panel, users, apply_sigmoid=True):
-    """rating[Bt, I] = act(user_panel[users] @ item_panel.T) — get_rating_for_test."""
-    _require_device(user_panel, item_panel, users)
-    U, V = _f32c(user_panel, "user_panel"), _f32c(item_panel, "item_panel")
-    users = _i64c(users, "users")
-    Bt, I, d = users.shape[0], V.shape[0], V.shape[1]
-    rating = torch.empty((Bt, I), dtype=torch.float32, device=V.device)
-    check(lib.idg_score_dense_f32(_ptr(U), _ptr(V), _ptr(users), Bt, I, d, int(bool(apply_sigmoid)), _ptr(rating),
-                                  _stream()), "idg_score_dense_f32")
-    return rating
-
-
-def topk_option(name, value=None):
-    """idg_score_topk_option: one of the process-wide knobs of score_topk's form choice — 'form' (-1 by geometry; 0 / 1 / 3),
-    'collect' (0: never the threshold + collect form), 'floor', 'wgs', 'chunks', 'fallback_permille' (form 3 hands a call
-    to the exact form beyond this share of users it cannot serve; < 0 never).  Returns the previous value; value None only
-    reads; name 'reset' restores every default.  The library reads IDG_TOPK_* from the environment once, at first use."""
-    from . import native
-
-    if name == "reset":
-        check(lib.idg_score_topk_option(native.IDG_TOPK_OPT_RESET, 0, None), "idg_score_topk_option")
-        return None
-    prev = C.c_int64()
-    check(lib.idg_score_topk_option(native.IDG_TOPK_OPTS[name][0], native.IDG_TOPK_OPT_KEEP if value is None else int(value),
-                                    C.byref(prev)), "idg_score_topk_option")
-    return int(prev.value)
-
-
-class topk_options:
-    """with ops.topk_options(collect=0): ... — knobs of score_topk's form choice for the duration of a block."""
-
-    def __init__(self, **values):
-        self.values, self.saved = values, {}
-
-    def __enter__(self):
-        for name, value in self.values.items():
-            self.saved[name] = topk_option(name, value)
-        return self
-
-    def __exit__(self, *exc):
-        for name, value in self.saved.items():
-            topk_option(name, value)
-        return False
-
-
-def score_topk_form(n_users, n_items, d, k):
-    """Which kernel a score_topk call of this geometry takes (idg_score_topk_info without a workspace):
-    {form: 0 alternating / 1 producer-consumer / 3 threshold + collect, chunks, floor}."""
-    out = (C.c_int64 * 8)()
-    check(lib.idg_score_topk_info(int(n_users), int(n_items), int(d), int(k), None, out, None), "idg_score_topk_info")
-    return {"form": int(out[0]), "chunks": int(out[1]), "floor": bool(out[2])}
-
-
-def score_topk(user_panel, item_panel, users, k, excl_indptr=None, excl_items=None, apply_sigmoid=True,
-               return_values=False, info=None):
-    """Top-k item ids per batch user, train positives masked to -1 (batch_test.py:59-68).
-    excl_indptr int64[num_users+1] / excl_items int32: DEVICE CSR of the train matrix.
-    info: a dict to fill with idg_score_topk_info's answer for this call (form, chunks, floor; form 3: users redone one by
-    one, users the finish could not serve, whether the call fell back to the exact form as a whole; synchronises)."""
-    _require_device(user_panel, item_panel, users, excl_indptr, excl_items)
-    U, V = _f32c(user_panel, "user_panel"), _f32c(item_panel, "item_panel")
-    users = _i64c(users, "users")
-    Bt, I, d = users.shape[0], V.shape[0], V.shape[1]
-    if excl_indptr is not None:
-        if excl_indptr.dtype != torch.int64 or excl_items.dtype != torch.int32:
-            raise TypeError("excl_indptr must be int64 and excl_items int32")
-    idx = torch.empty((Bt, k), dtype=torch.int64, device=V.device)
-    val = torch.empty((Bt, k), dtype=torch.float32, device=V.device) if return_values else None
-    # One library call per `per_call` users.  A user's list does not depend on who shares its call, and every test user in
-    # one call is what the kernels want — but the workspace grows with the call (the threshold + collect form keeps up to
-    # 1024 candidate keys per user: 8-16 KB each), so a call whose workspace would exceed the budget (IDG_TOPK_WS_BYTES,
-    # default 8 GiB: ~500,000 users) is cut into calls of a multiple of 16,384 users (256 user tiles: every CU keeps its own).
-    budget = int(os.environ.get("IDG_TOPK_WS_BYTES", str(8 << 30)))
-    per_call = Bt
-    if Bt > 32768 and int(lib.idg_score_topk_workspace_bytes(Bt, I, d, int(k))) > budget:
-        per_call = 16384
-        while per_call * 2 < Bt and int(lib.idg_score_topk_workspace_bytes(per_call * 2, I, d, int(k))) <= budget:
-            per_call *= 2
-    redone = unserved = fell_back = 0
-    cand_counts = []
-    for s0 in range(0, Bt, per_call):
-        n = min(per_call, Bt - s0)
-        ws = torch.empty(int(lib.idg_score_topk_workspace_bytes(n, I, d, int(k))), dtype=torch.uint8, device=V.device)
-        check(lib.idg_score_topk_f32(_ptr(U), _ptr(V), _ptr(users[s0:s0 + n]), n, I, d, _ptr(excl_indptr), _ptr(excl_items),
-                                     int(k), int(bool(apply_sigmoid)), _ptr(idx[s0:s0 + n]),
-                                     _ptr(val[s0:s0 + n]) if val is not None else None, _ptr(ws), _stream()),
-              "idg_score_topk_f32")
-        if info is not None:
-            out = (C.c_int64 * 8)()
-            check(lib.idg_score_topk_info(n, I, d, int(k), _ptr(ws), out, _stream()), "idg_score_topk_info")
-            redone += max(int(out[3]), 0)
-            unserved += max(int(out[4]), 0)
-            fell_back += max(int(out[5]), 0)
-            if s0 == 0:  # (form / chunks / floor of the first call: later ones differ only in a shorter last call)
-                info.update(form=int(out[0]), chunks=int(out[1]), floor=bool(out[2]), calls=-(-Bt // per_call))
-            info["users_redone"] = redone if int(out[3]) >= 0 else int(out[3])
-            if int(out[3]) >= 0:  # (form 3)
-                info.update(users_unserved=unserved, calls_fallen_back=fell_back, items_irregular=bool(out[6]))
-                if info.get("candidates") is not None and int(out[5]) == 0:  # (asked for: info = {"candidates": True})
-                    cnt = torch.empty(n, dtype=torch.int32, device=V.device)
-                    check(lib.idg_score_topk_candidate_counts(n, I, d, int(k), _ptr(ws), _ptr(cnt), _stream()),
-                          "idg_score_topk_candidate_counts")
-                    cand_counts.append(cnt)
-    if cand_counts:
-        c = torch.cat(cand_counts).float()
-        info["candidates"] = {"mean": float(c.mean()), "p50": float(c.quantile(0.5)) if c.numel() <= 16_000_000 else None,
-                              "p99": float(c.quantile(0.99)) if c.numel() <= 16_000_000 else None, "max": float(c.max())}
-    return (idx, val) if return_values else idx

@@ -6,7 +6,7 @@ import numpy as np
 class HipKernels:
     """`kernels` bound to libidgrec.so on the current HIP device.  The step issues ~40 library calls; what is marshalled
     here is kept minimal (the engine hands over the same preallocated buffers every step: pointers and views are cached,
-    arguments are not re-validated — ops.py's wrappers do that for everybody else)."""
+    arguments are not re-validated — the wrappers in ops/ do that for everybody else)."""
 
     def __init__(self, device=None):
         import ctypes as C

@@ -52,9 +52,16 @@ def traced(name, fn, stream_arg=None):
 
 
 def install_trace():
+    # a *_raw function is patched wherever its object is bound: idgrec_amd.ops and, where ops is a package, its submodules
+    # (the module that defines it and those that import it), so a call one wrapper makes to another is traced in both trees
+    homes = [m for key, m in sorted(sys.modules.items())
+             if m is not None and (key == ops.__name__ or key.startswith(ops.__name__ + "."))]
     for name, fn in list(vars(ops).items()):
         if name.endswith("_raw") and isinstance(fn, types.FunctionType):
-            setattr(ops, name, traced(name, fn))
+            call = traced(name, fn)
+            for m in homes:
+                if vars(m).get(name) is fn:
+                    setattr(m, name, call)
     for name, fn in list(vars(ops.Graph).items()):
         if isinstance(fn, types.FunctionType) and not name.startswith("_"):
             setattr(ops.Graph, name, traced("Graph." + name, fn))

@@ -634,8 +634,18 @@ def test_ngcf_transform_vs_float64(ops, n, d1, d2):
     assert torch.allclose(S, S2, rtol=1e-5, atol=1e-5)
 
 
+@pytest.fixture
+def compose_views(ops):
+    """compose_views(flag) sets ops._compose_views[0] — the list is mutated, never rebound: propagate_views_raw reads the name in
+    its own module — and False is put back after the test."""
+    def set_flag(composed):
+        ops._compose_views[0] = composed
+    yield set_flag
+    ops._compose_views[0] = False
+
+
 @pytest.mark.parametrize("d,K,n_views", [(64, 3, 2), (64, 2, 1), (256, 3, 2), (32, 4, 2)])
-def test_propagate_views_one_call_equals_composition(ops, d, K, n_views, monkeypatch):
+def test_propagate_views_one_call_equals_composition(ops, d, K, n_views, compose_views):
     """idg_propagate_views_f32 (shared first product, ONE multi-panel restricted launch for the last layer of all
     passes, per-panel last-arriver tickets for chunked rows) against the same passes assembled from idg_spmm_f32 /
     idg_perturb_f32 / idg_propagate_mean[_noise]_f32: identical bits, with and without a row bitmap."""
@@ -660,7 +670,7 @@ def test_propagate_views_one_call_equals_composition(ops, d, K, n_views, monkeyp
     for out_rows in (None, bm):
         res = []
         for composed in (False, True):
-            monkeypatch.setattr(ops, "_compose_views", [composed])
+            compose_views(composed)
             outs = [torch.full((n, d), float("nan"), device="cuda") for _ in range(n_views + 1)]
             ops.propagate_views_raw(G, E0, K, False, 0.1, streams, outs, out_rows=out_rows)
             res.append(outs)

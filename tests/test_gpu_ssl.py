@@ -290,15 +290,25 @@ VIEW_RUNS = [(c, r, False) for c in ONE_CALL for r in (False, True)] \
     + [(c, r, False) for c in ref.VIEWS_CASES if c not in ONE_CALL for r in (False, True)]
 
 
+@pytest.fixture
+def compose_views(ops):
+    """compose_views(flag) sets ops._compose_views[0] — the list is mutated, never rebound: propagate_views_raw reads the name in
+    its own module — and False is put back after the test."""
+    def set_flag(composed):
+        ops._compose_views[0] = composed
+    yield set_flag
+    ops._compose_views[0] = False
+
+
 @pytest.mark.parametrize("case_,restricted,composed", VIEW_RUNS)
-def test_views(ops, graphs, monkeypatch, case_, restricted, composed):
+def test_views(ops, graphs, compose_views, case_, restricted, composed):
     """The clean pass and the perturbed views of one call: idg_propagate_views_f32 (shared first product, one multi-panel launch
     for the last layer with a bitmap), the same passes composed from the single-purpose entry points, three views (the
     composition) and layer 0 in the mean (no shared product: idg_propagate_mean_noise_f32 per view)."""
     graph, K, inc, d, n_views = case_
     case = graphs[graph]
     assert ref.shares_first_product(K, inc, d) == (not inc)
-    monkeypatch.setattr(ops, "_compose_views", [composed])
+    compose_views(composed)
     w64, w32 = _views_expected(case, K, inc, d, n_views)
     rows, bm = _rows_of(case)
     sel = rows if restricted else torch.arange(case.n, device="cuda")
